@@ -3,7 +3,12 @@
 ("attention TFLOPS/sec/GPU fwd+bwd; cp=1->8 scaling at seqlen 64k") measured
 through the product path (magi_attention.api calc_attn) on synthetic data.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the contract line.
+--dump-outputs DIR additionally writes what the last timed step returned
+(out, lse, dq, dk, dv) as DIR/<name>.npy. --full adds the secondary
+measurements (dominant-kernel roofline, the extra BASELINE configs, the CPU
+baseline) to the line; without it those fields are null.
 N>1 is launched by the driver via torch.distributed.run (one rank per GPU,
 RCCL); this process then reads RANK/WORLD_SIZE from the env.
 
@@ -105,22 +110,27 @@ def run_bench(args):
     ql = dispatch(q, key).requires_grad_(True)
     kl = dispatch(k, key).requires_grad_(True)
     vl = dispatch(v, key).requires_grad_(True)
-    dout = torch.randn_like(ql)
+    # seeded like q/k/v, so two runs with the same arguments see the same inputs
+    gd = torch.Generator(device=device).manual_seed(4242 + rank)
+    dout = torch.randn(ql.shape, generator=gd, device=device, dtype=ql.dtype)
     del q, k, v
 
-    def step():
+    def step(keep=False):
         out, meta = calc_attn(ql, kl, vl, key)
         out.backward(dout)
+        last = (out, meta, ql.grad, kl.grad, vl.grad) if keep else None
         ql.grad = kl.grad = vl.grad = None
+        return last
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
+    last = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        last = step(keep=i == args.steps - 1)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -129,7 +139,33 @@ def run_bench(args):
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = STEP_FLOPS * args.steps / elapsed / 1e12  # whole-job TFLOPS/s
-    return rank, world, ms_per_step, value, device, (ql, kl, vl, dout, key)
+    return rank, world, ms_per_step, value, device, (ql, kl, vl, dout, key), last
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept per array (4 MiB as float32)
+
+
+def dump_outputs(last, dirname, rank, world):
+    """Write what the last timed step handed back to its caller (out, lse and
+    the q/k/v gradients) as <dirname>/<name>.npy in float32. Arrays larger than
+    DUMP_SAMPLE elements are reduced to a fixed, seeded sample of their
+    flattened elements, so two builds can be compared output for output."""
+    import numpy as np
+
+    out, meta, dq, dk, dv = last
+    arrays = {"out": out.detach(), "dq": dq, "dk": dk, "dv": dv}
+    if getattr(meta, "lse", None) is not None:
+        arrays["lse"] = meta.lse.detach()
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            gi = torch.Generator().manual_seed(1234)
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=gi)
+            flat = flat[idx.sort().values.to(flat.device)]
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"),
+                flat.float().cpu().numpy())
 
 
 def measure_roofline(state, device):
@@ -498,23 +534,37 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
-    ap.add_argument("--skip-extra-configs", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the extra configs and the "
+                         "CPU baseline (runs of their own after the timed steps)")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU baseline")
+    ap.add_argument("--skip-extra-configs", action="store_true",
+                    help="with --full: leave out the extra configs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     assert torch.cuda.is_available(), "bench.py needs an MI355X"
-    rank, world, ms_per_step, value, device, state = run_bench(args)
+    rank, world, ms_per_step, value, device, state, last = run_bench(args)
+    if args.dump_outputs:
+        dump_outputs(last, args.dump_outputs, rank, world)
+    del last
 
-    # all ranks participate (attn_fwd inside issues collectives); rank 0 reports
-    roofline = measure_roofline(state, device)
-    extra = None
-    if world == 1 and not args.skip_extra_configs:
-        try:
-            extra = measure_extra_configs(device)
-        except Exception as e:  # never fail the contract line
-            extra = {"error": repr(e)}
+    roofline = extra = cpu_baseline = None
+    if args.full:
+        # all ranks participate (attn_fwd inside issues collectives); rank 0 reports
+        roofline = measure_roofline(state, device)
+        if world == 1 and not args.skip_extra_configs:
+            try:
+                extra = measure_extra_configs(device)
+            except Exception as e:  # never fail the contract line
+                extra = {"error": repr(e)}
+        if rank == 0 and not args.skip_cpu_baseline:
+            cpu_baseline = measure_cpu_baseline()
     if rank == 0:
-        cpu_baseline = None if args.skip_cpu_baseline else measure_cpu_baseline()
         line = {
             "metric": "attention TFLOPS/sec fwd+bwd (whole-job; per-GPU = value/n_gpus); cp scaling at seqlen 64k",
             "value": value,
