@@ -28,6 +28,12 @@ SOURCES = [
     CSRC / "grpcoll.hip",
 ]
 
+# not compiled on their own, but part of the build stamp
+HEADERS = [
+    CSRC / "ffa_device.h",
+    PKG.parent / "include" / "magi_ffa.h",
+]
+
 HIPCC = "hipcc"
 FLAGS = [
     "--offload-arch=gfx950",
@@ -42,7 +48,7 @@ FLAGS = [
 
 def _source_digest() -> str:
     h = hashlib.sha256()
-    for s in sorted(SOURCES) + [PKG.parent / "include" / "magi_ffa.h"]:
+    for s in sorted(SOURCES) + HEADERS:
         if s.exists():
             h.update(s.read_bytes())
     h.update(" ".join(FLAGS).encode())

@@ -1,91 +1,44 @@
-// ffa_bwd.hip — MI355X-native flex-flash-attention BACKWARD (gfx950), v1.
+// ffa_bwd.hip — MI355X-native flex-flash-attention BACKWARD (gfx950).
 //
 // Behaviour: reference flash_bwd_kernel_sm90.h:41 /
 // mainloop_bwd_sm90_tma_gmma_ws.hpp (5-matmul recompute backward, fp32 atomic
 // dQ/dK/dV accumulation; preprocess dPsum = rowsum(dO*O),
 // flash_bwd_preprocess_kernel.h:42).
 //
-// Structure v1: ONE workgroup = 4 waves = 128 k rows (each wave one 32-row
-// k tile of the same range+head). The workgroup loops over the slice's q
-// tiles; per iteration Q[32][D] and dO[32][D] are staged ONCE into
-// XOR-swizzled LDS by all 256 threads (coalesced 16-B loads) and consumed by
-// all 4 waves — replacing v0's per-wave scalar global loads. Per wave:
-//   S^T  = K Q^T ; dP^T = V dO^T      (swapped MFMA, q-side operands from LDS)
-//   P^T, dS^T                          (base-2 recompute, like the fwd)
-//   dV  += P^T dO ; dK += dS^T Q       (P/dS transposed through per-wave LDS)
-//   dQ  += atomicAdd(dS K)             (dS^T -> A-frag in-register, permlane)
-// dK/dV accumulate in AGPRs across the q loop, atomic-added once at the end.
+// Three kernels, launched as separate passes by the host:
+//   bwd_preprocess_kernel  dpsum = rowsum(dO * O), one wave per (row, head).
+//   ffa_bwd_dq_kernel      q-outer: a workgroup of WAVES (4 or 8) waves owns
+//     WAVES x 32 q rows of one range+head; each wave keeps its Q/dO fragments
+//     and its dQ accumulator in registers and loops over the k range. K/V
+//     tiles (64 rows per barrier) are staged once per workgroup into
+//     XOR-swizzled LDS by global_load_lds and consumed by all waves:
+//       S^T = K Q^T ; dP^T = V dO^T ; dS^T (base-2 recompute, like the fwd)
+//       dQ += dS K   (dS^T -> A-frag in-register via permlane, K B-frags by
+//                     tr16 reads off the staged row image)
+//     dQ is atomic-added once at the end.
+//   ffa_bwd_dkv_kernel     k-outer: a workgroup owns WAVES x 32 k rows; each
+//     wave accumulates its dK and/or dV tile in registers over the q loop and
+//     atomic-adds it once at the end. Q/dO tiles are staged per iteration:
+//       S = Q K^T ; dP = dO V^T ; P, dS
+//       dV += P^T dO ; dK += dS^T Q   (P/dS -> A-frags in-register, dO/Q
+//                                      B-frags by tr16 reads)
+//     MODE 0 computes both (fused: K and V tiles live in LDS), MODE 1 only dV,
+//     MODE 2 only dK (split: K/V fragments live in registers).
+// 8 waves (one 512-thread workgroup per CU, 2 waves/SIMD) serve long ranges,
+// 4 waves short ranges and D=192; the launchers at the end of the file pick.
+// The staging ring depth (NBUF) is fixed by (MODE, WAVES) inside each kernel.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
-#include <type_traits>
 
 #include "../../include/magi_ffa.h"
+#include "ffa_device.h"
 
 #define BWD_BN 32    // k rows per wave
 #define BWD_BM 32    // q rows per tile
-#define BWD_WAVES 4  // k tiles per workgroup
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16_t = __bf16;
-
-#define DEV_INLINE __device__ __forceinline__
-
-// Software-pipelined LDS-DMA barrier: waits until at most VM vector-memory
-// ops are outstanding (= exactly the NEXT prefetch group, leaving the current
-// tile's group retired), makes LDS reads visible, then syncs the block.
-// vmcnt retires in issue order, so a constant distance works as long as every
-// iteration issues the same number of vector-memory ops — stage_glds is
-// therefore called unconditionally with clamped addresses past the end.
-// __syncthreads() would insert s_waitcnt vmcnt(0) and collapse the pipeline
-// to depth one (measured: 34-42%% SQ_WAIT in both backward kernels).
-template <int VM>
-DEV_INLINE void pipe_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier"
-               :: "n"(VM) : "memory");
-}
-
-DEV_INLINE int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 DEV_INLINE bool wave_alive(int m0, int qe) { return m0 < qe; }
-
-// ds_read_b64_tr_b16 pair -> one MFMA B-fragment (8 bf16).
-// Probed semantics (tests/gpu_probe_tr16.py): within each 16-lane group, the
-// addresses of lanes =0 (mod 4) give four ROW base addresses; lane l receives
-// element (row_j_base + (l&15)) for j=0..3. Two reads cover 8 rows.
-// r2: the r1 inline-asm version forced `s_waitcnt lgkmcnt(0)` + a sched
-// fence per fragment — a full ~50-cycle LDS-latency park before every second
-// MFMA of the output matmuls. The clang builtin is the same instruction but
-// scheduler-visible: reads pipeline across fragments and waits batch.
-DEV_INLINE bf16x8 tr16_frag(int a0, int a1) {
-  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_;
-  bf16x4_ v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (__attribute__((address_space(3))) bf16x4_*)(unsigned)a0);
-  bf16x4_ v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (__attribute__((address_space(3))) bf16x4_*)(unsigned)a1);
-  union {
-    bf16x4_ h[2];
-    bf16x8 v;
-  } r;
-  r.h[0] = v0;
-  r.h[1] = v1;
-  return r.v;
-}
-
-// one packed convert (RNE, same as the scalar bf16 cast) — the C version
-// lowers to 2 cvt + shift + or, 4x the issue slots (guide: cvt_pk idiom)
-DEV_INLINE unsigned pack_bf16_pair(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-// raw v_exp_f32: the libm exp2f expands to ~5 instructions of denormal-range
-// guards; specials (inf/NaN) behave identically, only sub-denormal precision
-// differs (P < 1e-38 ~ 0)
-DEV_INLINE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 DEV_INLINE bf16x8 cframe_to_afrag(const float* val, int tt) {
   unsigned c0 = pack_bf16_pair(val[8 * tt + 0], val[8 * tt + 1]);
@@ -131,7 +84,6 @@ struct BwdParams {
   float scale;
   float softcap;
   long long total_q, total_k;
-  int debug_ablate;  // perf ablation only: 1=skip dq stores, 2=skip dkv stores
   int head_major;    // 1: blockIdx.x = head (XCD-affine); 0: work-major
   int work_nx, work_ny, work_nz;  // flattened work space (strided-grid mode)
   int head_mult;     // deterministic GQA split: real head = off + idx*mult
@@ -176,27 +128,23 @@ __global__ __launch_bounds__(256) void bwd_preprocess_kernel(BwdParams p, int d,
 // when forced to 256). Shares S, P, exp2 and the staged Q/dO image between
 // the dV and dK matmuls: 32 MFMAs per subtile vs the split modes' 40.
 // MODE 1: dV only / MODE 2: dK only — the r1 split, kept selectable.
-// WAVES: k-tiles per workgroup sharing ONE staged Q/dO image.
-// NBUF: LDS staging ring depth. 2 = r1 behaviour (barrier drains vmcnt(0),
-// prefetch has one compute phase to land). 3 = constant-distance vmcnt(G)
-// barrier: prefetch has TWO compute phases, and the barrier only waits for
-// the one stage it needs — attacks the 34-42% SQ_WAIT_ANY of the r1 PMC.
-template <int D, bool HAS_SOFTCAP, int MODE, int WAVES, int NBUF, int NT = 0>
-__global__ __launch_bounds__(64 * WAVES, WAVES >= 6 ? 2 : 1)
+// WAVES: k-tiles per workgroup sharing ONE staged Q/dO image (4 or 8; the
+// D=192 builds spill at 8 waves' 256-register cap and exist at 4 only).
+// NBUF: LDS staging ring depth. 2 = barrier drains vmcnt(0), prefetch has
+// one compute phase to land. 3 = constant-distance vmcnt(G) barrier:
+// prefetch has TWO compute phases, and the barrier only waits for the one
+// stage it needs — attacks the 34-42% SQ_WAIT_ANY of the r1 PMC. The split
+// 8-wave kernels run the 3-ring; the fused mode keeps 2 (its K/V tiles + a
+// 3-ring exceed the 160 KB LDS), and so do 4-wave workgroups (3 buffers
+// exceed the 80 KB/WG budget of 2 blocks/CU).
+template <int D, bool HAS_SOFTCAP, int MODE, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1)
 void ffa_bwd_dkv_kernel(BwdParams p) {
-  // NT: stage with the non-temporal policy (aux=2) — staged rows are read
-  // once per WG; keeping them out of L2 protects the resident K strips and
-  // V tiles from streaming eviction (PMC: 174 GB/launch L2-miss traffic)
-  constexpr int STAGE_AUX = NT ? 2 : 0;
+  static_assert(WAVES == 4 || (WAVES == 8 && D != 192), "unsupported shape");
+  constexpr int NBUF = (MODE != 0 && WAVES == 8) ? 3 : 2;
   constexpr bool WANT_DV = MODE != 2;
   constexpr bool WANT_DK = MODE != 1;
-  // MODE 3 = fused "fat wave" (r2-v3): 4 waves x 64 k rows (2 column tiles)
-  // at 1 wave/SIMD — the unified 512-reg file holds BOTH columns' dK/dV
-  // accumulators (256 regs -> AGPRs), 64 MFMAs per wave between barriers
-  // instead of 32, and half the waves to sync per barrier. Same 256-row
-  // k span per WG as MODE 0 at 8 waves, identical grid.
-  constexpr bool V_IN_LDS = (MODE == 0 || MODE == 3);
-  constexpr int NCOL = (MODE == 3) ? 2 : 1;
+  constexpr bool V_IN_LDS = MODE == 0;
   constexpr int DF = D / 16;
   constexpr int DT = D / 32;
   // LDS rows padded to a power of two (D=192 -> 512-byte rows; see
@@ -237,7 +185,7 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   const int h = p.head_off + hidx * p.head_mult;
   const int wb = p.head_major ? wy : wx;
   const int ks = p.k_ranges[2 * ri], ke = p.k_ranges[2 * ri + 1];
-  const int nblk0 = ks + wb * (BWD_BN * NCOL * WAVES);
+  const int nblk0 = ks + wb * (BWD_BN * WAVES);
   if (nblk0 >= ke) continue;
   const int seg0 = p.seg_starts ? p.seg_starts[ri] : ri;
   const int seg1 = p.seg_starts ? p.seg_starts[ri + 1] : ri + 1;
@@ -254,9 +202,8 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   const int lo32 = lane & 31;
   const int hi = lane >> 5;
 
-  const int n0 = nblk0 + wave * (BWD_BN * NCOL);  // this wave's k tile(s)
+  const int n0 = nblk0 + wave * BWD_BN;  // this wave's k tile
   const bool wave_live = n0 < ke;
-  const bool skip_dq = (p.debug_ablate & 1) != 0;
 
   const float sl2 = HAS_SOFTCAP ? p.softcap * 1.4426950408889634f
                                 : p.scale * 1.4426950408889634f;
@@ -286,13 +233,12 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   // scheduler slack below the 256 cap.
   // (the 32-row ring is only needed at D=128, where the K/V tiles take
   // 128 KB; at D=64 everything fits beside a 64-row ring)
-  // Ring depth: the fused modes' K/V tiles crowd the ring out of LDS at
-  // D=128 when the WG spans 256 k rows (W8, or W4x2col); the W6 fused
-  // variant (192 k rows -> 96 KB of tiles) fits a 64-row ring exactly.
+  // Ring rows: the fused mode's K/V tiles crowd the 64-row ring out of LDS
+  // at D=128 when the WG spans 256 k rows (W8).
   constexpr int QITER =
-      (V_IN_LDS && D == 128 && WAVES * NCOL >= 8) ? BWD_BM : 2 * BWD_BM;
+      (V_IN_LDS && D == 128 && WAVES == 8) ? BWD_BM : 2 * BWD_BM;
   constexpr int NSUB = QITER / BWD_BM;
-  constexpr int KVLDS = V_IN_LDS ? 2 * WAVES * NCOL * BWD_BN * ROWB : 0;
+  constexpr int KVLDS = V_IN_LDS ? 2 * WAVES * BWD_BN * ROWB : 0;
   constexpr int LSELDS = V_IN_LDS ? 0 : NBUF * 2 * QITER * 4;
   static_assert(NBUF * 2 * QITER * ROWB + LSELDS + KVLDS <= 163840,
                 "LDS budget");
@@ -313,10 +259,10 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   // MODE 0: per-wave K and V tiles (BWD_BN rows x D, same 32-B XOR swizzle
   // as the Q/dO images so the A-fragment reads reuse the qf addressing)
   __bf16* lds_kt = (__bf16*)(smem + NBUF * 2 * QITER * ROWB + LSELDS) +
-                   wave * NCOL * BWD_BN * ROWE;
+                   wave * BWD_BN * ROWE;
   __bf16* lds_vt = (__bf16*)(smem + NBUF * 2 * QITER * ROWB + LSELDS +
                              KVLDS / 2) +
-                   wave * NCOL * BWD_BN * ROWE;
+                   wave * BWD_BN * ROWE;
 
   // K fragments (A-layout), loaded once per block; V fragments likewise in
   // the split dK mode — the fused mode stages V into LDS instead (register
@@ -341,7 +287,7 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   constexpr int ROWS_PER_GLDS_V = 1024 / ROWB;
   if constexpr (V_IN_LDS) {
 #pragma unroll
-    for (int gi = 0; gi < (NCOL * BWD_BN) / ROWS_PER_GLDS_V; ++gi) {
+    for (int gi = 0; gi < BWD_BN / ROWS_PER_GLDS_V; ++gi) {
       const int r0v = ROWS_PER_GLDS_V * gi;
       const int r = r0v + lane / (ROWB / 16);
       const int c = lane % (ROWB / 16);
@@ -353,17 +299,17 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
           (const __attribute__((address_space(1))) unsigned int*)(
               p.k + (size_t)kr * k_pitch + (size_t)kh * D + csw),
           (__attribute__((address_space(3))) unsigned int*)&lds_kt[r0v * ROWE],
-          16, 0, STAGE_AUX);
+          16, 0, 0);
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) unsigned int*)(
               p.v + (size_t)kr * k_pitch + (size_t)kh * D + csw),
           (__attribute__((address_space(3))) unsigned int*)&lds_vt[r0v * ROWE],
-          16, 0, STAGE_AUX);
+          16, 0, 0);
     }
   }
 
   // block + wave q loop bounds (recomputed per q segment)
-  const int nlast = min(nblk0 + BWD_BN * NCOL * WAVES, ke) - 1;
+  const int nlast = min(nblk0 + BWD_BN * WAVES, ke) - 1;
   int q_lo = 0, q_hi = 0, wq_lo = 0, wq_hi = 0;
   auto seg_bounds = [&]() {
     q_lo = qs; q_hi = qe;
@@ -372,12 +318,12 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
     wq_lo = qs; wq_hi = qe;
     if (atype == 1 || atype == 3) wq_lo = max(wq_lo, n0 - (ke - qe));
     if (atype == 2 || atype == 3)
-      wq_hi = min(wq_hi, (n0 + NCOL * BWD_BN - 1) - (ks - qs) + 1);
+      wq_hi = min(wq_hi, (n0 + BWD_BN - 1) - (ks - qs) + 1);
   };
 
-  f32x16 acc_dk[WANT_DK ? NCOL * DT : 1], acc_dv[WANT_DV ? NCOL * DT : 1];
+  f32x16 acc_dk[WANT_DK ? DT : 1], acc_dv[WANT_DV ? DT : 1];
 #pragma unroll
-  for (int dt = 0; dt < NCOL * DT; ++dt) {
+  for (int dt = 0; dt < DT; ++dt) {
     if constexpr (WANT_DK) acc_dk[dt] = (f32x16)(0.f);
     if constexpr (WANT_DV) acc_dv[dt] = (f32x16)(0.f);
   }
@@ -407,12 +353,12 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
           (const __attribute__((address_space(1))) unsigned int*)(
               p.q + (size_t)qrow * q_pitch + (size_t)h * D + csw),
           (__attribute__((address_space(3))) unsigned int*)&lds_q(buf)[r0 * ROWE],
-          16, 0, STAGE_AUX);
+          16, 0, 0);
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) unsigned int*)(
               p.dout + (size_t)qrow * q_pitch + (size_t)h * D + csw),
           (__attribute__((address_space(3))) unsigned int*)&lds_do(buf)[r0 * ROWE],
-          16, 0, STAGE_AUX);
+          16, 0, 0);
     }
     // lse (lanes 0-31) / dpsum (lanes 32-63), one LDS-DMA per 32-row group
     // (MODE 0 has no LDS lse region: compute reads them into lane registers
@@ -427,7 +373,7 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
             (const __attribute__((address_space(1))) unsigned int*)src,
             (__attribute__((address_space(3))) unsigned int*)(
                 lds_lse(buf) + sg * 2 * BWD_BM),
-            4, 0, STAGE_AUX);
+            4, 0, 0);
       }
     }
   };
@@ -486,13 +432,6 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
     };
 
     if (wave_live && ms + BWD_BM > wq_lo && ms < wq_hi) {
-      // MODE 3: the wave's two 32-column tiles in sequence — each column has
-      // its own C tiles and accumulator slice; Q/dO fragments and the lse /
-      // dpsum selects are re-read per column (LDS/lane-local, cheap), the
-      // barrier/staging cost is paid once for both.
-#pragma unroll
-      for (int ch = 0; ch < NCOL; ++ch) {
-      const int nch = n0 + ch * BWD_BN;
       // ---- S = Q K^T ; dP = dO V^T, UN-swapped: C layout [q=crow][k=lo32],
       // so the dV/dK A-fragments come from the in-register permlane transform
       // (cframe) instead of an LDS round-trip ----
@@ -501,8 +440,8 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
         // fused mode: K and V fragments come straight off the wave's LDS
         // tiles (staged once per block) — identical addressing to qf. The
         // two independent MFMA streams cover each other's LDS read latency.
-        const char* kt_c = (const char*)(lds_kt + ch * BWD_BN * ROWE);
-        const char* vt_c = (const char*)(lds_vt + ch * BWD_BN * ROWE);
+        const char* kt_c = (const char*)lds_kt;
+        const char* vt_c = (const char*)lds_vt;
 #pragma unroll
         for (int dd = 0; dd < DF; ++dd) {
           const int off = swz(lo32, lo32 * ROWB + dd * 32 + hi * 16);
@@ -526,16 +465,16 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
       }
       }
 
-      const int kk = nch + lo32;  // this lane's k column
+      const int kk = n0 + lo32;  // this lane's k column
       // S is dead once P is computed, dP once dS is — reuse their registers
       // (all indices are compile-time constants after unrolling, so the
       // pointer cast stays in VGPRs; checked: ScratchSize 0)
       float* pv = (float*)&s;
       float* dsv = (float*)&dp;
       const bool interior =
-          (ms + BWD_BM <= wq_hi) && (ms >= qs) && (nch + BWD_BN <= ke) &&
-          !((atype == 1 || atype == 3) && (nch + BWD_BN - 1 > ms + (ke - qe))) &&
-          !((atype == 2 || atype == 3) && (nch < ms + BWD_BM - 1 + (ks - qs)));
+          (ms + BWD_BM <= wq_hi) && (ms >= qs) && (n0 + BWD_BN <= ke) &&
+          !((atype == 1 || atype == 3) && (n0 + BWD_BN - 1 > ms + (ke - qe))) &&
+          !((atype == 2 || atype == 3) && (n0 < ms + BWD_BM - 1 + (ks - qs)));
       bool all_live = interior;
       if (interior) {
 #pragma unroll
@@ -628,10 +567,10 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
         };
         if constexpr (MODE == 1) {
           pipe_mm(do_base, cframe_to_afrag(pv, 0), cframe_to_afrag(pv, 1),
-                  acc_dv + ch * DT);
+                  acc_dv);
         } else if constexpr (MODE == 2) {
           pipe_mm(q_base, cframe_to_afrag(dsv, 0), cframe_to_afrag(dsv, 1),
-                  acc_dk + ch * DT);
+                  acc_dk);
         } else {
           // MODE 0 (fused dK+dV): INTERLEAVE the two independent MFMA
           // streams — each fragment load's LDS latency is covered by the
@@ -644,28 +583,26 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
           bf16x8 da1 = cframe_to_afrag(dsv, 1);
 #pragma unroll
           for (int dt = 0; dt < DT; ++dt) {
-            const int at = ch * DT + dt;
             const int dcol = (dt * 32 + 16 * qhalf) * 2;
             bf16x8 bdo = tr16_frag(do_base + rb0 + (dcol ^ sw0),
                                    do_base + rb1 + (dcol ^ sw1));
-            acc_dv[at] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                pa0, bdo, acc_dv[at], 0, 0, 0);
+            acc_dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                pa0, bdo, acc_dv[dt], 0, 0, 0);
             bf16x8 bq = tr16_frag(q_base + rb0 + (dcol ^ sw0),
                                   q_base + rb1 + (dcol ^ sw1));
-            acc_dk[at] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                da0, bq, acc_dk[at], 0, 0, 0);
+            acc_dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                da0, bq, acc_dk[dt], 0, 0, 0);
             bf16x8 bdo1 = tr16_frag(do_base + rb2 + (dcol ^ sw2),
                                     do_base + rb3 + (dcol ^ sw3));
-            acc_dv[at] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                pa1, bdo1, acc_dv[at], 0, 0, 0);
+            acc_dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                pa1, bdo1, acc_dv[dt], 0, 0, 0);
             bf16x8 bq1 = tr16_frag(q_base + rb2 + (dcol ^ sw2),
                                    q_base + rb3 + (dcol ^ sw3));
-            acc_dk[at] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                da1, bq1, acc_dk[at], 0, 0, 0);
+            acc_dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                da1, bq1, acc_dk[dt], 0, 0, 0);
           }
         }
       }
-      }  // ch (column tile)
     }
     }  // sub
     cur = (NBUF == 3) ? (cur == 2 ? 0 : cur + 1) : (cur ^ 1);
@@ -674,30 +611,27 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   }  // seg
 
   // ---- write dK/dV ----
-  if (wave_live && !(p.debug_ablate & 2)) {
-#pragma unroll
-  for (int ch = 0; ch < NCOL; ++ch) {
+  if (wave_live) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int kr = n0 + ch * BWD_BN + crow(r, hi);
+    const int kr = n0 + crow(r, hi);
     if (kr >= ke) continue;
     float* dkp = p.dk + (size_t)kr * k_pitch + (size_t)kh * D;
     float* dvp = p.dv + (size_t)kr * k_pitch + (size_t)kh * D;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       if constexpr (WANT_DK) {
-        if (acc_dk[ch * DT + dt][r] != 0.f)
-          unsafeAtomicAdd(dkp + dt * 32 + lo32, acc_dk[ch * DT + dt][r]);
+        if (acc_dk[dt][r] != 0.f)
+          unsafeAtomicAdd(dkp + dt * 32 + lo32, acc_dk[dt][r]);
       }
       if constexpr (WANT_DV) {
-        if (acc_dv[ch * DT + dt][r] != 0.f)
-          unsafeAtomicAdd(dvp + dt * 32 + lo32, acc_dv[ch * DT + dt][r]);
+        if (acc_dv[dt][r] != 0.f)
+          unsafeAtomicAdd(dvp + dt * 32 + lo32, acc_dv[dt][r]);
       }
     }
   }
-  }  // ch
   }  // wave_live store
-  if constexpr (MODE == 0 || MODE == 3) break;  // single trip: kills the backedge (regs)
+  if constexpr (MODE == 0) break;  // single trip: kills the backedge (regs)
   }  // strided work loop
 }
 
@@ -709,10 +643,15 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
 // ablation measured at ~45% of a fused backward. K/V tiles are staged
 // cooperatively per iteration (row-major swizzled for the S^T/dP^T A-frags,
 // plus a transposed copy for the dQ B-frags).
-template <int D, bool HAS_SOFTCAP, int WAVES, int NBUF, int NT = 0>
+// WAVES: q tiles per workgroup sharing ONE staged K/V image (4 or 8; the
+// D=192 builds spill at 8 waves' 256-register cap and exist at 4 only).
+// 8 waves run the 3-slot staging ring (see the dkv kernel note); 4 waves keep
+// 2 slots (3 buffers exceed the 80 KB/WG budget of 2 blocks/CU).
+template <int D, bool HAS_SOFTCAP, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2)
 void ffa_bwd_dq_kernel(BwdParams p) {
-  constexpr int STAGE_AUX = NT ? 2 : 0;  // see dkv kernel note
+  static_assert(WAVES == 4 || (WAVES == 8 && D != 192), "unsupported shape");
+  constexpr int NBUF = WAVES == 8 ? 3 : 2;
   constexpr int DF = D / 16;
   constexpr int DT = D / 32;
   constexpr int ROWB = (D == 192) ? 512 : D * 2;  // padded pow2 LDS rows
@@ -759,7 +698,6 @@ void ffa_bwd_dq_kernel(BwdParams p) {
   const int qrow = m0 + lo32;
   const bool qvalid = qrow < qe && m0 < qe;
   const int qcl = qvalid ? qrow : (qe - 1);
-  const bool skip_dq = (p.debug_ablate & 1) != 0;
 
   const float sl2 = HAS_SOFTCAP ? p.softcap * 1.4426950408889634f
                                 : p.scale * 1.4426950408889634f;
@@ -833,12 +771,12 @@ void ffa_bwd_dq_kernel(BwdParams p) {
           (const __attribute__((address_space(1))) unsigned int*)(
               p.k + (size_t)kr * k_pitch + (size_t)kh * D + csw),
           (__attribute__((address_space(3))) unsigned int*)&lds_k(buf)[r0 * ROWE],
-          16, 0, STAGE_AUX);
+          16, 0, 0);
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) unsigned int*)(
               p.v + (size_t)kr * k_pitch + (size_t)kh * D + csw),
           (__attribute__((address_space(3))) unsigned int*)&lds_v(buf)[r0 * ROWE],
-          16, 0, STAGE_AUX);
+          16, 0, 0);
     }
   };
 
@@ -968,7 +906,6 @@ void ffa_bwd_dq_kernel(BwdParams p) {
   }  // seg
 
   // ---- store dq once (atomicAdd: q_ranges of different slices may overlap) ----
-  if (!skip_dq) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int qr = m0 + crow(r, hi);
@@ -980,283 +917,9 @@ void ffa_bwd_dq_kernel(BwdParams p) {
       if (val != 0.f) unsafeAtomicAdd(dst + dt * 32 + lo32, val);
     }
   }
-  }  // !skip_dq
   }  // strided work loop
 }
 
-
-// ---------------- dQ pass, 64-row q tiles (r2) ----------------
-// Each wave owns a 64-row q tile as two interleaved 32-row halves at ONE
-// wave/SIMD (512-reg budget). Why this beats the 32-row/2-wave shape:
-// every K/V fragment read (b128 A-frags and tr16 B-frags) is SHARED by the
-// two halves' MFMAs — memory ops per MFMA halve — and the two halves are
-// independent MFMA streams, so each read's LDS latency hides under the
-// other half's matrix op without a partner wave.
-template <int D, bool HAS_SOFTCAP, int NBUF, int NT = 0>
-__global__ __launch_bounds__(256, 1)
-void ffa_bwd_dq64_kernel(BwdParams p) {
-  constexpr int STAGE_AUX = NT ? 2 : 0;
-  constexpr int DF = D / 16;
-  constexpr int DT = D / 32;
-  constexpr int ROWB = D * 2;
-  constexpr int SW32M = ROWB / 32 - 1;
-  constexpr int WAVES = 4;
-  constexpr int TQ = 64;  // q rows per wave
-  auto swz = [](int row, int byte_off) {
-    return byte_off ^ ((row & SW32M) << 5);
-  };
-  const int ri = blockIdx.z;
-  const int h = p.head_major ? blockIdx.x : blockIdx.y;
-  const int wb = p.head_major ? blockIdx.y : blockIdx.x;
-  const int qs = p.q_ranges[2 * ri], qe = p.q_ranges[2 * ri + 1];
-  const int mblk0 = qs + wb * (TQ * WAVES);
-  if (mblk0 >= qe) return;
-  const int seg0 = p.seg_starts ? p.seg_starts[ri] : ri;
-  const int seg1 = p.seg_starts ? p.seg_starts[ri + 1] : ri + 1;
-  int ks, ke, atype;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int lo32 = lane & 31;
-  const int hi = lane >> 5;
-
-  const int m0 = mblk0 + wave * TQ;  // this wave's 64-row q tile
-  const bool skip_dq = (p.debug_ablate & 1) != 0;
-
-  const float sl2 = HAS_SOFTCAP ? p.softcap * 1.4426950408889634f
-                                : p.scale * 1.4426950408889634f;
-  const float cap_pre = HAS_SOFTCAP ? p.scale / p.softcap : 0.f;
-  const float log2e = 1.4426950408889634f;
-
-  const int kh = h / p.gqa;
-  const size_t k_pitch = (size_t)p.hk * D;
-  const size_t q_pitch = (size_t)p.hq * D;
-
-  constexpr int KITER = 2 * BWD_BN;
-  static_assert(NBUF * 2 * KITER * D * 2 <= 163840, "LDS budget");
-  __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * KITER * D * 2];
-  auto lds_k = [&](int buf) -> __bf16* {
-    return (__bf16*)(smem + (2 * buf) * KITER * D * 2);
-  };
-  auto lds_v = [&](int buf) -> __bf16* {
-    return (__bf16*)(smem + (2 * buf + 1) * KITER * D * 2);
-  };
-
-  // persistent per-wave operands, both halves
-  bf16x8 qf[2][DF], dof[2][DF];
-  float lse_q[2], dpsum_q[2];
-  bool row_live[2], qvalid[2];
-  int qrow_h[2];
-#pragma unroll
-  for (int hh = 0; hh < 2; ++hh) {
-    const int qrow = m0 + 32 * hh + lo32;
-    qrow_h[hh] = qrow;
-    qvalid[hh] = qrow < qe;
-    const int qcl = qvalid[hh] ? qrow : (qe - 1);
-    const bf16_t* qp = p.q + (size_t)qcl * q_pitch + (size_t)h * D;
-    const bf16_t* dp = p.dout + (size_t)qcl * q_pitch + (size_t)h * D;
-#pragma unroll
-    for (int dd = 0; dd < DF; ++dd) {
-      qf[hh][dd] = *(const bf16x8*)(qp + dd * 16 + hi * 8);
-      dof[hh][dd] = *(const bf16x8*)(dp + dd * 16 + hi * 8);
-    }
-    lse_q[hh] = qvalid[hh] ? p.lse[(size_t)qrow * p.hq + h] : INFINITY;
-    dpsum_q[hh] = qvalid[hh] ? p.dpsum[(size_t)qrow * p.hq + h] : 0.f;
-    row_live[hh] = qvalid[hh] && lse_q[hh] != INFINITY &&
-                   lse_q[hh] != -INFINITY;
-  }
-
-  const int mlast = min(mblk0 + TQ * WAVES, qe) - 1;
-  int k_lo = 0, k_hi = 0, wk_lo = 0, wk_hi = 0;
-  auto seg_bounds = [&]() {
-    k_lo = ks; k_hi = ke;
-    if (atype == 1 || atype == 3) k_hi = min(k_hi, mlast + (ke - qe) + 1);
-    if (atype == 2 || atype == 3) k_lo = max(k_lo, mblk0 + (ks - qs));
-    wk_lo = ks; wk_hi = ke;
-    if (atype == 1 || atype == 3)
-      wk_hi = min(wk_hi, min(m0 + TQ, qe) - 1 + (ke - qe) + 1);
-    if (atype == 2 || atype == 3) wk_lo = max(wk_lo, m0 + (ks - qs));
-  };
-
-  f32x16 acc_dq[2][DT];
-#pragma unroll
-  for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) acc_dq[hh][dt] = (f32x16)(0.f);
-
-  constexpr int ROWS_PER_GLDS = 1024 / ROWB;
-  constexpr int GLDS_PER_WAVE = (KITER / WAVES) / ROWS_PER_GLDS;
-  auto stage_glds = [&](int buf, int n0x) {
-#pragma unroll
-    for (int gi = 0; gi < GLDS_PER_WAVE; ++gi) {
-      const int r0 = (KITER / WAVES) * wave + ROWS_PER_GLDS * gi;
-      const int r = r0 + lane / (ROWB / 16);
-      const int c = lane % (ROWB / 16);
-      const int kr = min(n0x + r, ke - 1);
-      const int csw = (c ^ ((r & SW32M) << 1)) * 8;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(
-              p.k + (size_t)kr * k_pitch + (size_t)kh * D + csw),
-          (__attribute__((address_space(3))) unsigned int*)&lds_k(buf)[r0 * D],
-          16, 0, STAGE_AUX);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(
-              p.v + (size_t)kr * k_pitch + (size_t)kh * D + csw),
-          (__attribute__((address_space(3))) unsigned int*)&lds_v(buf)[r0 * D],
-          16, 0, STAGE_AUX);
-    }
-  };
-
-  constexpr int GOPS = 2 * GLDS_PER_WAVE;
-  int cur = 0;
-  for (int seg = seg0; seg < seg1; ++seg) {
-  ks = p.k_ranges[2 * seg];
-  ke = p.k_ranges[2 * seg + 1];
-  atype = p.attn_type_map ? p.attn_type_map[seg] : 0;
-  if (ke <= ks) continue;
-  seg_bounds();
-  if (k_lo >= k_hi) continue;
-  cur = 0;
-  stage_glds(0, k_lo);
-  if constexpr (NBUF == 3) stage_glds(1, k_lo + KITER);
-
-  for (int n0 = k_lo; n0 < k_hi; n0 += KITER) {
-    pipe_barrier<NBUF == 3 ? GOPS : 0>();
-    if constexpr (NBUF == 3) {
-      stage_glds(cur == 0 ? 2 : cur - 1, n0 + 2 * KITER);
-    } else {
-      if (n0 + KITER < k_hi) stage_glds(cur ^ 1, n0 + KITER);
-    }
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-    const int ns = n0 + sub * BWD_BN;
-    if (ns >= k_hi) break;
-    const __bf16* lkb = lds_k(cur) + sub * BWD_BN * D;
-    const __bf16* lvb = lds_v(cur) + sub * BWD_BN * D;
-
-    if (m0 < qe && ns + BWD_BN > wk_lo && ns < wk_hi) {
-      // ---- S^T / dP^T for BOTH halves off ONE kf/vf read pair ----
-      f32x16 sA0 = (f32x16)(0.f), dpA0 = (f32x16)(0.f);
-      f32x16 sA1 = (f32x16)(0.f), dpA1 = (f32x16)(0.f);
-#pragma unroll
-      for (int dd = 0; dd < DF; ++dd) {
-        const int off = swz(lo32, lo32 * ROWB + dd * 32 + hi * 16);
-        bf16x8 kf = *(const bf16x8*)((const char*)lkb + off);
-        bf16x8 vf = *(const bf16x8*)((const char*)lvb + off);
-        sA0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[0][dd], sA0, 0, 0, 0);
-        dpA0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[0][dd], dpA0, 0, 0, 0);
-        sA1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[1][dd], sA1, 0, 0, 0);
-        dpA1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[1][dd], dpA1, 0, 0, 0);
-      }
-
-      // ---- softmax recompute per half; `scale` folded into the FINAL dq
-      // store (dq is linear in dS), not the per-element dsv ----
-      float dsv[2][16];
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        const f32x16& sA = hh ? sA1 : sA0;
-        const f32x16& dpA = hh ? dpA1 : dpA0;
-        const int m0h = m0 + 32 * hh;
-        const bool interior =
-            (qrow_h[hh] < qe) && row_live[hh] && (ns >= ks) &&
-            (ns + BWD_BN <= ke) &&
-            !((atype == 1 || atype == 3) &&
-              (ns + BWD_BN - 1 > m0h + (ke - qe))) &&
-            !((atype == 2 || atype == 3) && (ns < m0h + 31 + (ks - qs)));
-        if (__all(interior) && !HAS_SOFTCAP) {
-          const float lsc = lse_q[hh] * log2e;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float pij = fast_exp2(sA[r] * sl2 - lsc);
-            dsv[hh][r] = pij * (dpA[r] - dpsum_q[hh]);
-          }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int kk = ns + crow(r, hi);
-            bool ok = row_live[hh] && kk < ke && kk >= ks;
-            if (atype == 1 || atype == 3)
-              ok = ok && (kk - qrow_h[hh] <= ke - qe);
-            if (atype == 2 || atype == 3)
-              ok = ok && (kk - qrow_h[hh] >= ks - qs);
-            float sv = sA[r];
-            float drel = 1.f;
-            float t;
-            if (HAS_SOFTCAP) {
-              const float th = tanhf(sv * cap_pre);
-              t = th * sl2;
-              drel = 1.f - th * th;
-            } else {
-              t = sv * sl2;
-            }
-            const float pij = ok ? fast_exp2(t - lse_q[hh] * log2e) : 0.f;
-            dsv[hh][r] = pij * (dpA[r] - dpsum_q[hh]) * drel;
-          }
-        }
-      }
-
-      // ---- dq += dS K: ONE tr16 B-frag feeds BOTH halves' MFMAs ----
-      bf16x8 a00 = cframe_to_afrag(dsv[0], 0);
-      bf16x8 a01 = cframe_to_afrag(dsv[0], 1);
-      bf16x8 a10 = cframe_to_afrag(dsv[1], 0);
-      bf16x8 a11 = cframe_to_afrag(dsv[1], 1);
-      {
-        const int qhalf2 = (lane >> 4) & 1;
-        const int jrow = (lane & 15) >> 2;
-        const int row0 = 8 * hi + jrow;
-        const int row1 = 8 * hi + 4 + jrow;
-        const int k_base = (int)(unsigned long long)(
-            (__attribute__((address_space(3))) const char*)lkb);
-        const int lane8 = (lane & 3) * 8;
-        const int sw0 = (row0 & SW32M) << 5;
-        const int sw1 = (row1 & SW32M) << 5;
-        const int rb0 = row0 * ROWB + lane8;
-        const int rb1 = row1 * ROWB + lane8;
-        const int sw2 = ((row0 + 16) & SW32M) << 5;
-        const int sw3 = ((row1 + 16) & SW32M) << 5;
-        const int rb2 = (row0 + 16) * ROWB + lane8;
-        const int rb3 = (row1 + 16) * ROWB + lane8;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          const int dcol = (dt * 32 + 16 * qhalf2) * 2;
-          bf16x8 b0 = tr16_frag(k_base + rb0 + (dcol ^ sw0),
-                                k_base + rb1 + (dcol ^ sw1));
-          acc_dq[0][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              a00, b0, acc_dq[0][dt], 0, 0, 0);
-          acc_dq[1][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              a10, b0, acc_dq[1][dt], 0, 0, 0);
-          bf16x8 b1 = tr16_frag(k_base + rb2 + (dcol ^ sw2),
-                                k_base + rb3 + (dcol ^ sw3));
-          acc_dq[0][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              a01, b1, acc_dq[0][dt], 0, 0, 0);
-          acc_dq[1][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              a11, b1, acc_dq[1][dt], 0, 0, 0);
-        }
-      }
-    }
-    }  // sub
-    cur = (NBUF == 3) ? (cur == 2 ? 0 : cur + 1) : (cur ^ 1);
-  }
-  __syncthreads();
-  }  // seg
-
-  if (skip_dq) return;
-#pragma unroll
-  for (int hh = 0; hh < 2; ++hh) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int qr = m0 + 32 * hh + crow(r, hi);
-      if (qr >= qe) continue;
-      float* dst = p.dq + (size_t)qr * q_pitch + (size_t)h * D;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const float val = acc_dq[hh][dt][r] * p.scale;
-        if (val != 0.f) unsafeAtomicAdd(dst + dt * 32 + lo32, val);
-      }
-    }
-  }
-}
 
 // ---------------- launchers ----------------
 extern "C" int magi_ffa_bwd_preprocess(const magi_ffa_bwd_args* a) {
@@ -1304,14 +967,6 @@ static int fill_bwd_params(const magi_ffa_bwd_args* a, BwdParams* p) {
   p->total_q = a->total_q;
   p->total_k = a->total_k;
   p->seg_starts = a->seg_starts;
-  { const char* e = getenv("MAGI_BWD_ABLATE"); p->debug_ablate = e ? atoi(e) : 0; }
-  // head-major pays when one head's K+V (bf16) fits a 4 MB XCD L2
-  // late-r2 A/B (profiles/r2_headmajor_ab.md): dq wins head-major up to
-  // ~16 MB of per-head K+V (1.20x at 16k) and loses beyond (0.93x at 64k,
-  // 0.91x at 128k) — same shape as the fwd kernel; the dkv launcher
-  // OVERRIDES this to always-head-major below.
-  p->head_major = ((long long)a->total_k * a->d * 4 <= (16 << 20)) ? 1 : 0;
-  { const char* e = getenv("MAGI_BWD_HEAD_MAJOR"); if (e) p->head_major = atoi(e); }
   // deterministic-mode GQA split: cu_margin's top bits carry (mult<<8)|off;
   // 0 = all heads in one launch (default)
   p->head_mult = 1;
@@ -1325,92 +980,109 @@ static int fill_bwd_params(const magi_ffa_bwd_args* a, BwdParams* p) {
   return 0;
 }
 
+// A/B knobs are read at EVERY launch: the head-major A/B scripts
+// (tests/gpu_headmajor_ab*.py) toggle them inside one process.
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// CU-margin (see ffa_fwd.hip): cap the grid below the resident-WG count;
+// each WG then walks the flattened work space p.work_n*.
+static dim3 cap_grid(dim3 grid, int margin, int wg_per_cu) {
+  if (margin <= 0) return grid;
+  const long long total = (long long)grid.x * grid.y * grid.z;
+  long long cap = (long long)(256 - margin) * wg_per_cu;
+  if (cap < 1) cap = 1;
+  if (cap > total) cap = total;
+  return dim3((unsigned)cap, 1, 1);
+}
+
+struct BwdKnobs {
+  int head_major;  // grid order: 1 = blockIdx.x is the head
+  int bigseq;      // k range length from which 8 waves run
+};
+
+static BwdKnobs dq_knobs(const magi_ffa_bwd_args* a) {
+  // head-major pays when one head's K+V (bf16) fits a 4 MB XCD L2
+  // late-r2 A/B (profiles/r2_headmajor_ab.md): dq wins head-major up to
+  // ~16 MB of per-head K+V (1.20x at 16k) and loses beyond (0.93x at 64k,
+  // 0.91x at 128k) — same shape as the fwd kernel.
+  const int hm = ((long long)a->total_k * a->d * 4 <= (16 << 20)) ? 1 : 0;
+  // 8 waves share one staged K/V image (one 512-thread WG/CU, 2 waves/SIMD)
+  // for LONG ranges: halves staging+barrier cost per MFMA (measured
+  // 67->63 ms at 64k). Short ranges keep 4 waves — dq's q-outer 256-row
+  // blocks over-iterate masked causal k windows on 2k varlen docs (r2 A/B:
+  // 0.79 -> 1.61 ms at W8).
+  return {env_int("MAGI_BWD_HEAD_MAJOR", hm),
+          env_int("MAGI_BWD_DQ_BIGSEQ", 8192)};
+}
+
+template <int D>
+static void launch_dq(int waves, bool sc, dim3 grid, hipStream_t s,
+                      const BwdParams& p) {
+#define GO(SC, W)                                                          \
+  hipLaunchKernelGGL((ffa_bwd_dq_kernel<D, SC, W>), grid, dim3(64 * W), 0, \
+                     s, p)
+  if constexpr (D != 192) {  // D=192 spills at 8 waves: 4-wave builds only
+    if (waves == 8) {
+      if (sc) GO(true, 8); else GO(false, 8);
+      return;
+    }
+  }
+  if (sc) GO(true, 4); else GO(false, 4);
+#undef GO
+}
+
 extern "C" int magi_ffa_bwd_dq(const magi_ffa_bwd_args* a) {
   BwdParams p;
   int rc = fill_bwd_params(a, &p);
   if (rc) return rc > 0 ? 0 : rc;
-
-  // 8 waves share one staged K/V image (one 512-thread WG/CU, 2 waves/SIMD)
-  // for LONG ranges: halves staging+barrier cost per MFMA (measured
-  // 67->63 ms at 64k). Short ranges keep 4 waves — the 256-row block
-  // windows over-iterate masked edges on 2k varlen docs.
-  // W8 runs the 3-slot LDS ring (constant-distance vmcnt barrier); W4 cannot
-  // (3 buffers exceed the 80 KB/WG budget of 2 blocks/CU) and keeps 2.
-  // dq's q-outer blocks DO over-iterate causal k windows at W8 (r2 A/B on
-  // 2k varlen: 0.79 -> 1.61 ms), so it keeps the long-range threshold
-  int dq_bigseq = 8192;
-  { const char* e = getenv("MAGI_BWD_DQ_BIGSEQ"); if (e) dq_bigseq = atoi(e); }
-  // D=192 W8 builds spill at the 256-reg cap: stay at 4 waves there
-  const int dqw = (a->d != 192 && a->max_seqlen_k >= dq_bigseq) ? 8 : 4;
-  int nbuf = 3;
-  { const char* e = getenv("MAGI_BWD_NBUF"); if (e) nbuf = atoi(e); }
-  int nt = 0;
-  { const char* e = getenv("MAGI_STAGE_NT"); if (e) nt = atoi(e); }
-  // measured 61.1 vs 54.8 ms at 64k: without a partner wave the exposed
-  // LDS/barrier latencies outweigh the halved memory ops — keep 2 waves/SIMD
-  int dq64 = 0;
-  { const char* e = getenv("MAGI_BWD_DQ64"); if (e) dq64 = atoi(e); }
+  const BwdKnobs knobs = dq_knobs(a);
+  p.head_major = knobs.head_major;
+  const int W = (a->d != 192 && a->max_seqlen_k >= knobs.bigseq) ? 8 : 4;
   if (a->n_ranges > 65535) return -5;
+  const int qspan = BWD_BM * W;
+  const int qblocks = (int)((a->total_q + qspan - 1) / qspan);
+  dim3 grid = p.head_major ? dim3(a->hq, qblocks, (unsigned)a->n_ranges)
+                           : dim3(qblocks, a->hq, (unsigned)a->n_ranges);
+  p.work_nx = grid.x; p.work_ny = grid.y; p.work_nz = grid.z;
+  grid = cap_grid(grid, a->cu_margin & 0xFFFF, W == 4 ? 2 : 1);
   hipStream_t s = (hipStream_t)a->stream;
   const bool sc = a->softcap > 0.f;
-  if (dqw == 8 && dq64 && a->d != 192) {
-    // 64-row q tiles, 4 waves, 1 wave/SIMD (same 256-row block span)
-    const int qblocks64 = (int)((a->total_q + 255) / 256);
-    dim3 grid64 = p.head_major
-                      ? dim3(a->hq, qblocks64, (unsigned)a->n_ranges)
-                      : dim3(qblocks64, a->hq, (unsigned)a->n_ranges);
-    p.work_nx = grid64.x; p.work_ny = grid64.y; p.work_nz = grid64.z;
-    dim3 block64(256);
-#define LAUNCH_DQ64(DD, SC) \
-  hipLaunchKernelGGL((ffa_bwd_dq64_kernel<DD, SC, 3>), grid64, block64, 0, s, p)
-    if (a->d == 64) { if (sc) LAUNCH_DQ64(64, true); else LAUNCH_DQ64(64, false); }
-    else            { if (sc) LAUNCH_DQ64(128, true); else LAUNCH_DQ64(128, false); }
-#undef LAUNCH_DQ64
-    return (int)hipGetLastError();
-  }
-  const int qspan = BWD_BM * dqw;
-  const int qblocks = (int)((a->total_q + qspan - 1) / qspan);
-  dim3 grid_q = p.head_major ? dim3(a->hq, qblocks, (unsigned)a->n_ranges)
-                             : dim3(qblocks, a->hq, (unsigned)a->n_ranges);
-  p.work_nx = grid_q.x; p.work_ny = grid_q.y; p.work_nz = grid_q.z;
-  const int margin = a->cu_margin & 0xFFFF;
-  if (margin > 0) {  // CU-margin: cap resident WGs (see ffa_fwd.hip)
-    const long long total = (long long)grid_q.x * grid_q.y * grid_q.z;
-    const int per_cu = (dqw == 4) ? 2 : 1;
-    long long cap = (long long)(256 - margin) * per_cu;
-    if (cap < 1) cap = 1;
-    if (cap > total) cap = total;
-    grid_q = dim3((unsigned)cap, 1, 1);
-  }
-  dim3 block(64 * dqw);
-#define LAUNCH_DQ(DD, SC, WW, NB, NTV) \
-  hipLaunchKernelGGL((ffa_bwd_dq_kernel<DD, SC, WW, NB, NTV>), grid_q, block, \
-                     0, s, p)
-#define PICK_DQ_NT(DD, NTV) \
-  do { \
-    if (dqw == 8) { \
-      bool done3 = false; \
-      if constexpr (DD != 192) { /* a 3-ring of 512-B rows exceeds LDS */ \
-        if (nbuf == 3) { \
-          if (sc) LAUNCH_DQ(DD, true, 8, 3, NTV); else LAUNCH_DQ(DD, false, 8, 3, NTV); \
-          done3 = true; \
-        } \
-      } \
-      if (!done3) { \
-        if (sc) LAUNCH_DQ(DD, true, 8, 2, NTV); else LAUNCH_DQ(DD, false, 8, 2, NTV); \
-      } \
-    } else { \
-      if (sc) LAUNCH_DQ(DD, true, 4, 2, NTV); else LAUNCH_DQ(DD, false, 4, 2, NTV); \
-    } \
-  } while (0)
-#define PICK_DQ(DD) do { if (nt) PICK_DQ_NT(DD, 1); else PICK_DQ_NT(DD, 0); } while (0)
-  if (a->d == 64) PICK_DQ(64);
-  else if (a->d == 192) PICK_DQ(192);
-  else PICK_DQ(128);
-#undef PICK_DQ
-#undef PICK_DQ_NT
-#undef LAUNCH_DQ
+  if (a->d == 64) launch_dq<64>(W, sc, grid, s, p);
+  else if (a->d == 192) launch_dq<192>(W, sc, grid, s, p);
+  else launch_dq<128>(W, sc, grid, s, p);
   return (int)hipGetLastError();
+}
+
+static BwdKnobs dkv_knobs() {
+  // dkv passes win head-major at EVERY measured size (their dk/dv atomics
+  // cluster per head in one XCD's L2): 1.54x at 16k, 1.10x at 64k, 1.07x
+  // at 128k (profiles/r2_headmajor_ab.md) — unconditional unless A/B'd.
+  // All dkv modes run 8 waves per WG (one 512-thread WG/CU, one shared
+  // staged Q/dO image) down to 1k ranges: these kernels' blocks span the
+  // K dim, so the wider workgroup does NOT over-iterate causal q windows,
+  // and halving the staging streams is a 50-60% win even on 2k varlen docs
+  // (r2 A/B: dv 0.71->0.48 ms, dk 0.90->0.56, fused 1.37->0.92; PMC r2: dV
+  // at W4 fetched 174 GB/launch vs dK-W8's 71).
+  return {env_int("MAGI_BWD_HEAD_MAJOR", 1), env_int("MAGI_BWD_BIGSEQ", 1024)};
+}
+
+template <int D, int MODE>
+static void launch_dkv(int waves, bool sc, dim3 grid, hipStream_t s,
+                       const BwdParams& p) {
+#define GO(SC, W)                                                        \
+  hipLaunchKernelGGL((ffa_bwd_dkv_kernel<D, SC, MODE, W>), grid,         \
+                     dim3(64 * W), 0, s, p)
+  if constexpr (D != 192) {  // D=192 spills at 8 waves: 4-wave builds only
+    if (waves == 8) {
+      if (sc) GO(true, 8); else GO(false, 8);
+      return;
+    }
+  }
+  if (sc) GO(true, 4); else GO(false, 4);
+#undef GO
 }
 
 template <int MODE>
@@ -1418,107 +1090,26 @@ static int launch_bwd_dkv(const magi_ffa_bwd_args* a) {
   BwdParams p;
   int rc = fill_bwd_params(a, &p);
   if (rc) return rc > 0 ? 0 : rc;
-  // dkv passes win head-major at EVERY measured size (their dk/dv atomics
-  // cluster per head in one XCD's L2): 1.54x at 16k, 1.10x at 64k, 1.07x
-  // at 128k (profiles/r2_headmajor_ab.md) — unconditional unless A/B'd
-  if (!getenv("MAGI_BWD_HEAD_MAJOR")) p.head_major = 1;
-  // All dkv modes run 8 waves per WG (one 512-thread WG/CU, one shared
-  // staged Q/dO image) down to 1k ranges: these kernels' blocks span the
-  // K dim, so the wider workgroup does NOT over-iterate causal q windows,
-  // and halving the staging streams is a 50-60% win even on 2k varlen docs
-  // (r2 A/B: dv 0.71->0.48 ms, dk 0.90->0.56, fused 1.37->0.92). The fused
-  // mode keeps NBUF=2 (its V tiles + a 3-ring exceed the 160 KB LDS); the
-  // split W8 modes default to the 3-slot ring.
-  int bigseq = 1024;
-  { const char* e = getenv("MAGI_BWD_BIGSEQ"); if (e) bigseq = atoi(e); }
-  const bool big = a->d != 192 && a->max_seqlen_k >= bigseq;
-  // W8 for ALL modes on long ranges: one 512-thread WG/CU halves the
-  // staging streams (PMC r2: dV at W4 fetched 174 GB/launch vs dK-W8's 71)
-  const int W = big ? 8 : 4;
-  // MODE 3 "fat" fused: 4 waves x 2 column tiles at 1 wave/SIMD (same
-  // 256-row span/grid as MODE 0 at W8) — A/B gate, see kernel note
-  int fat = 0;
-  { const char* e = getenv("MAGI_BWD_FAT"); if (e) fat = atoi(e); }
-  const bool use_fat = (MODE == 0) && big && fat != 0;
-  // W6 fused: 192-row k span, 64-row Q/dO ring (2x the MFMAs per barrier of
-  // the W8 32-row ring), 1.5 waves/SIMD — A/B gate
-  int w6 = 0;
-  { const char* e = getenv("MAGI_BWD_W6"); if (e) w6 = atoi(e); }
-  const bool use_w6 = (MODE == 0) && big && !use_fat && w6 != 0;
-  int nbuf = (MODE == 0 || W == 4) ? 2 : 3;
-  { const char* e = getenv("MAGI_BWD_NBUF");
-    if (e && nbuf == 3) nbuf = atoi(e); }
-  int nt = 0;
-  { const char* e = getenv("MAGI_STAGE_NT"); if (e) nt = atoi(e); }
-  const int span =
-      use_fat ? (2 * 4 * BWD_BN) : (use_w6 ? 6 * BWD_BN : BWD_BN * W);
+  const BwdKnobs knobs = dkv_knobs();
+  p.head_major = knobs.head_major;
+  const int W = (a->d != 192 && a->max_seqlen_k >= knobs.bigseq) ? 8 : 4;
+  const int span = BWD_BN * W;
   const int nblocks = (a->max_seqlen_k + span - 1) / span;
   if (a->n_ranges > 65535) return -5;
-  dim3 grid_kv = p.head_major
-                     ? dim3(p.n_heads_launch, nblocks, (unsigned)a->n_ranges)
-                     : dim3(nblocks, p.n_heads_launch, (unsigned)a->n_ranges);
-  p.work_nx = grid_kv.x; p.work_ny = grid_kv.y; p.work_nz = grid_kv.z;
-  const int margin = (MODE == 0) ? 0 : (a->cu_margin & 0xFFFF);
-  if (margin > 0) {  // CU-margin: cap resident WGs (see ffa_fwd.hip)
-    const long long total = (long long)grid_kv.x * grid_kv.y * grid_kv.z;
-    const int per_cu = (W == 4 && MODE != 0) ? 2 : 1;
-    long long cap = (long long)(256 - margin) * per_cu;
-    if (cap < 1) cap = 1;
-    if (cap > total) cap = total;
-    grid_kv = dim3((unsigned)cap, 1, 1);
-  }
-  dim3 block(use_fat ? 256 : (use_w6 ? 384 : 64 * W));
+  dim3 grid = p.head_major
+                  ? dim3(p.n_heads_launch, nblocks, (unsigned)a->n_ranges)
+                  : dim3(nblocks, p.n_heads_launch, (unsigned)a->n_ranges);
+  p.work_nx = grid.x; p.work_ny = grid.y; p.work_nz = grid.z;
+  // the fused kernel's work loop is single-trip (see kernel): never capped
+  if constexpr (MODE != 0)
+    grid = cap_grid(grid, a->cu_margin & 0xFFFF, W == 4 ? 2 : 1);
   hipStream_t s = (hipStream_t)a->stream;
   const bool sc = a->softcap > 0.f;
-#define LAUNCH_DKV(DD, SC, WW, NB, NTV) \
-  hipLaunchKernelGGL((ffa_bwd_dkv_kernel<DD, SC, MODE, WW, NB, NTV>), grid_kv, \
-                     block, 0, s, p)
-#define LAUNCH_FAT(DD, SC, NTV) \
-  hipLaunchKernelGGL((ffa_bwd_dkv_kernel<DD, SC, 3, 4, 2, NTV>), grid_kv, \
-                     block, 0, s, p)
-#define LAUNCH_W6(DD, SC, NTV) \
-  hipLaunchKernelGGL((ffa_bwd_dkv_kernel<DD, SC, 0, 6, 2, NTV>), grid_kv, \
-                     block, 0, s, p)
-#define PICK_DKV_NT(DD, NTV) \
-  do { \
-    if (use_fat) { \
-      if constexpr (MODE == 0 && DD != 192) { \
-        if (sc) LAUNCH_FAT(DD, true, NTV); else LAUNCH_FAT(DD, false, NTV); \
-        break; \
-      } \
-    } \
-    if (use_w6) { \
-      if constexpr (MODE == 0 && DD != 192) { \
-        if (sc) LAUNCH_W6(DD, true, NTV); else LAUNCH_W6(DD, false, NTV); \
-        break; \
-      } \
-    } \
-    if (W == 8) { \
-      bool done = false; \
-      if constexpr (MODE != 0 && DD != 192) { /* 3-ring LDS limits */ \
-        if (nbuf == 3) { \
-          if (sc) LAUNCH_DKV(DD, true, 8, 3, NTV); else LAUNCH_DKV(DD, false, 8, 3, NTV); \
-          done = true; \
-        } \
-      } \
-      if (!done) { \
-        if (sc) LAUNCH_DKV(DD, true, 8, 2, NTV); else LAUNCH_DKV(DD, false, 8, 2, NTV); \
-      } \
-    } else { \
-      if (sc) LAUNCH_DKV(DD, true, 4, 2, NTV); else LAUNCH_DKV(DD, false, 4, 2, NTV); \
-    } \
-  } while (0)
-#define PICK_DKV(DD) do { if (nt) PICK_DKV_NT(DD, 1); else PICK_DKV_NT(DD, 0); } while (0)
-  if (a->d == 64) PICK_DKV(64);
+  if (a->d == 64) launch_dkv<64, MODE>(W, sc, grid, s, p);
   else if (a->d == 192) {
-    if constexpr (MODE != 0) PICK_DKV(192);
+    if constexpr (MODE != 0) launch_dkv<192, MODE>(W, sc, grid, s, p);
     else return -6;  // fused + D=192 exceeds LDS; host routes to the split
-  } else PICK_DKV(128);
-#undef PICK_DKV
-#undef PICK_DKV_NT
-#undef LAUNCH_W6
-#undef LAUNCH_FAT
-#undef LAUNCH_DKV
+  } else launch_dkv<128, MODE>(W, sc, grid, s, p);
   return (int)hipGetLastError();
 }
 

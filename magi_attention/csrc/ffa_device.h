@@ -1,0 +1,72 @@
+// ffa_device.h — device helpers shared by the FFA kernels (gfx950, wave64):
+// vector typedefs, the software-pipelined LDS-DMA barrier, and the MFMA
+// 32x32x16 fragment helpers. Included by ffa_fwd.hip, ffa_bwd.hip,
+// ffa_index.hip and ffa_fwd_fp8.hip; everything here is force-inlined.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using bf16_t = __bf16;
+
+#define DEV_INLINE __device__ __forceinline__
+
+// Software-pipelined LDS-DMA barrier: waits until at most VM vector-memory
+// ops are outstanding (= exactly the NEXT prefetch group, leaving the current
+// tile's group retired), makes LDS reads visible, then syncs the block.
+// vmcnt retires in issue order, so a constant distance works as long as every
+// iteration issues the same number of vector-memory ops and the loop issues
+// NO other vector-memory ops — the staging lambdas are therefore called
+// unconditionally with clamped addresses past the end.
+// __syncthreads() would insert s_waitcnt vmcnt(0) and collapse the pipeline
+// to depth one (measured: 34-42% SQ_WAIT in both backward kernels).
+template <int VM>
+DEV_INLINE void pipe_barrier() {
+  asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier"
+               :: "n"(VM) : "memory");
+}
+
+DEV_INLINE float warp_xor32(float v) { return __shfl_xor(v, 32, 64); }
+
+// one packed convert (RNE, same as the scalar bf16 cast) — the C version
+// lowers to 2 cvt + shift + or, 4x the issue slots (guide: cvt_pk idiom)
+DEV_INLINE unsigned pack_bf16_pair(float lo, float hi) {
+  unsigned r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+
+// raw v_exp_f32: the libm exp2f expands to ~5 instructions of denormal-range
+// guards; specials (inf/NaN) behave identically, only sub-denormal precision
+// differs (P < 1e-38 ~ 0)
+DEV_INLINE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// C/D fragment row for v_mfma_f32_32x32x16_bf16: reg r, lane-half hi
+DEV_INLINE int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+
+// ds_read_b64_tr_b16 pair -> one MFMA B-fragment (8 bf16).
+// Probed semantics (tests/gpu_probe_tr16.py): within each 16-lane group, the
+// addresses of lanes =0 (mod 4) give four ROW base addresses; lane l receives
+// element (row_j_base + (l&15)) for j=0..3. Two reads cover 8 rows. The rows'
+// 32-B runs must be physically contiguous, hence the 32-B-granular swizzle
+// of the staged row images.
+// The clang builtin rather than inline asm: an asm read forces
+// `s_waitcnt lgkmcnt(0)` + a sched fence per fragment — a full ~50-cycle
+// LDS-latency park before every second MFMA of the output matmuls. The
+// builtin is the same instruction but scheduler-visible: reads pipeline
+// across fragments and waits batch.
+DEV_INLINE bf16x8 tr16_frag(int a0, int a1) {
+  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_;
+  bf16x4_ v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (__attribute__((address_space(3))) bf16x4_*)(unsigned)a0);
+  bf16x4_ v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (__attribute__((address_space(3))) bf16x4_*)(unsigned)a1);
+  union {
+    bf16x4_ h[2];
+    bf16x8 v;
+  } r;
+  r.h[0] = v0;
+  r.h[1] = v1;
+  return r.v;
+}

@@ -26,65 +26,11 @@
 #include <math.h>
 
 #include "../../include/magi_ffa.h"
+#include "ffa_device.h"
 
 #define FFA_BM 128   // q rows per workgroup (4 waves x 32)
 #define FFA_BN 32    // k rows per inner tile
 #define LOCK_GRAN 128
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16_t = __bf16;
-
-#define DEV_INLINE __device__ __forceinline__
-
-// Software-pipelined LDS-DMA barrier (see ffa_bwd.hip): wait until at most
-// VM vector-memory ops are outstanding (the one prefetch stage this wave
-// still has in flight), instead of the full vmcnt(0) drain __syncthreads()
-// would insert. Valid because the k loop issues NO other vector-memory ops.
-template <int VM>
-DEV_INLINE void fwd_pipe_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier"
-               ::"i"(VM) : "memory");
-}
-
-DEV_INLINE float warp_xor32(float v) { return __shfl_xor(v, 32, 64); }
-
-// one packed convert (RNE, same as the scalar bf16 cast) — the C version
-// lowers to 2 cvt + shift + or, 4x the issue slots (guide: cvt_pk idiom)
-DEV_INLINE unsigned pack_bf16_pair(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-// raw v_exp_f32: the libm exp2f expands to ~5 instructions of denormal-range
-// guards; specials (inf/NaN) behave identically, only sub-denormal precision
-// differs (P < 1e-38 ~ 0)
-DEV_INLINE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// C/D fragment row for v_mfma_f32_32x32x16_bf16: reg r, lane-half hi
-DEV_INLINE int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-// ds_read_b64_tr_b16 pair -> one MFMA B-fragment (see ffa_bwd.hip for the
-// probed semantics).
-// r2: the r1 inline-asm version forced `s_waitcnt lgkmcnt(0)` + a sched
-// fence per fragment — a full ~50-cycle LDS-latency park before every second
-// MFMA of the output matmuls. The clang builtin is the same instruction but
-// scheduler-visible: reads pipeline across fragments and waits batch.
-DEV_INLINE bf16x8 tr16_frag(int a0, int a1) {
-  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_;
-  bf16x4_ v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (__attribute__((address_space(3))) bf16x4_*)(unsigned)a0);
-  bf16x4_ v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (__attribute__((address_space(3))) bf16x4_*)(unsigned)a1);
-  union {
-    bf16x4_ h[2];
-    bf16x8 v;
-  } r;
-  r.h[0] = v0;
-  r.h[1] = v1;
-  return r.v;
-}
 
 struct FwdParams {
   const bf16_t* q;
@@ -431,7 +377,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
       // NBUF=3: wait ONLY for buf[cur] (leave the next stage in flight),
       // then prefetch two stages ahead — always, with clamped rows, so the
       // vmcnt distance stays constant. NBUF=2: full drain.
-      fwd_pipe_barrier<NBUF == 3 ? GOPS : 0>();
+      pipe_barrier<NBUF == 3 ? GOPS : 0>();
       if constexpr (NBUF == 3) {
         stage_glds(cur == 0 ? 2 : cur - 1, n0 + 2 * KITER);
       } else {

@@ -22,20 +22,13 @@
 #include <math.h>
 
 #include "../../include/magi_ffa.h"
+#include "ffa_device.h"
 
 #define FP8_BM 128
 #define FP8_BN 32
 #define LOCK_GRAN 128
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 using u8 = unsigned char;
-
-#define DEV_INLINE __device__ __forceinline__
-
-DEV_INLINE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-DEV_INLINE float warp_xor32(float v) { return __shfl_xor(v, 32, 64); }
-DEV_INLINE int crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 DEV_INLINE u8 to_fp8(float x) {
   // f32 -> e4m3 via the packed convert (lower byte)

@@ -27,41 +27,9 @@
 #include <math.h>
 
 #include "../../include/magi_ffa.h"
+#include "ffa_device.h"
 
 #define IDX_BN 32  // k rows per inner MFMA tile
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16_t = __bf16;
-
-#define DEV_INLINE __device__ __forceinline__
-
-DEV_INLINE float idx_warp_xor32(float v) { return __shfl_xor(v, 32, 64); }
-
-DEV_INLINE unsigned idx_pack_bf16_pair(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-DEV_INLINE float idx_fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-DEV_INLINE int idx_crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-
-DEV_INLINE bf16x8 idx_tr16_frag(int a0, int a1) {
-  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_;
-  bf16x4_ v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (__attribute__((address_space(3))) bf16x4_*)(unsigned)a0);
-  bf16x4_ v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (__attribute__((address_space(3))) bf16x4_*)(unsigned)a1);
-  union {
-    bf16x4_ h[2];
-    bf16x8 v;
-  } r;
-  r.h[0] = v0;
-  r.h[1] = v1;
-  return r.v;
-}
 
 struct IdxParams {
   const bf16_t* q;
@@ -211,7 +179,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int kk = ns + idx_crow(r, hi);
+        const int kk = ns + crow(r, hi);
         const bool ok = qvalid && (kk < count);
         float sv = s[r];
         if (HAS_SOFTCAP) sv = tanhf(sv * cap_pre);
@@ -219,7 +187,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
         mx = fmaxf(mx, t[r]);
       }
     }
-    mx = fmaxf(mx, idx_warp_xor32(mx));
+    mx = fmaxf(mx, warp_xor32(mx));
 
     // ---- defer-max (see ffa_fwd.hip) ----
     const float m_new = fmaxf(m_run, mx);
@@ -232,7 +200,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
       alpha = 1.f;
     } else {
       m_use = (m_new == -INFINITY) ? 0.f : m_new;
-      alpha = (m_run == -INFINITY) ? 0.f : idx_fast_exp2(m_run - m_use);
+      alpha = (m_run == -INFINITY) ? 0.f : fast_exp2(m_run - m_use);
       m_run = m_new;
     }
 
@@ -240,15 +208,15 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     float psum = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      pr[r] = idx_fast_exp2(t[r] - m_use);
+      pr[r] = fast_exp2(t[r] - m_use);
       psum += pr[r];
     }
-    l_run = l_run * alpha + (psum + idx_warp_xor32(psum));
+    l_run = l_run * alpha + (psum + warp_xor32(psum));
 
     if (__any(alpha != 1.f)) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int src = idx_crow(r, hi);
+        const int src = crow(r, hi);
         const float aq = __uint_as_float(
             __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(alpha)));
 #pragma unroll
@@ -260,10 +228,10 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     bf16x8 pa[2];
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
-      unsigned c0 = idx_pack_bf16_pair(pr[8 * tt + 0], pr[8 * tt + 1]);
-      unsigned c1 = idx_pack_bf16_pair(pr[8 * tt + 2], pr[8 * tt + 3]);
-      unsigned c2 = idx_pack_bf16_pair(pr[8 * tt + 4], pr[8 * tt + 5]);
-      unsigned c3 = idx_pack_bf16_pair(pr[8 * tt + 6], pr[8 * tt + 7]);
+      unsigned c0 = pack_bf16_pair(pr[8 * tt + 0], pr[8 * tt + 1]);
+      unsigned c1 = pack_bf16_pair(pr[8 * tt + 2], pr[8 * tt + 3]);
+      unsigned c2 = pack_bf16_pair(pr[8 * tt + 4], pr[8 * tt + 5]);
+      unsigned c3 = pack_bf16_pair(pr[8 * tt + 6], pr[8 * tt + 7]);
       {
         auto r2 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
         c0 = r2[0];
@@ -303,7 +271,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
           const int dcol = (dt * 32 + 16 * qhalf) * 2;
-          bf16x8 bv = idx_tr16_frag(rb0 + (dcol ^ sw0), rb1 + (dcol ^ sw1));
+          bf16x8 bv = tr16_frag(rb0 + (dcol ^ sw0), rb1 + (dcol ^ sw1));
           acc_o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[tt], bv,
                                                               acc_o[dt], 0, 0, 0);
         }
@@ -335,7 +303,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     p.lse[tok * p.hq + qh] = lse_new;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int src = idx_crow(r, hi);
+    const int src = crow(r, hi);
     const float ilq = __uint_as_float(
         __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(inv_l)));
     const int qr = q0 + src;

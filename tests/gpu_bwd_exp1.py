@@ -1,6 +1,6 @@
-"""r2 experiment 1: solo backward-pass timings at 64k dense causal across
-kernel variants (split NBUF2 = r1 baseline, split NBUF3 ring, fused-dkv r2),
-plus fwd 8k/64k reference points. Prints ms per launch + effective TFLOPS of
+"""r2 experiment 1: solo backward-pass timings at 64k dense causal (dq, split
+dv/dk, fused dkv), plus fwd 8k/64k reference points; also the case/args/timing
+helpers the head-major A/B and PMC workload scripts import. Prints ms per launch + effective TFLOPS of
 the ISSUED matmul work (dq pass issues 3/5 of bwd FLOPs, dv 2/5... wait:
 dq = S,dP,dQ = 3 units; dv = S,dV = 2; dk = S,dP,dK = 3; fused = S,dP,dV,dK = 4;
 one 'unit' = fwd_flops/2)."""
@@ -83,14 +83,13 @@ def main():
         print(f"{tag:28s} {ms:8.2f} ms   issued {tf:7.1f} TF/s ({eff:4.1f}% peak)")
 
     print(f"== 64k causal h{hq} d{d}: one matmul unit = {unit/1e12:.2f} TFLOP ==")
-    run("dq64 (1 wave/SIMD)", "magi_ffa_bwd_dq", 3)
-    run("dq32 (2 waves)", "magi_ffa_bwd_dq", 3, {"MAGI_BWD_DQ64": "0"})
+    run("dq", "magi_ffa_bwd_dq", 3)
     run("dv  W8", "magi_ffa_bwd_dv", 2)
     run("dk", "magi_ffa_bwd_dk", 3)
     run("dkv fused", "magi_ffa_bwd_dkv", 4)
 
-    # best-combo whole-backward estimate
-    best_dq = min(results["dq64 (1 wave/SIMD)"][0], results["dq32 (2 waves)"][0])
+    # whole-backward estimate
+    best_dq = results["dq"][0]
     split = results["dv  W8"][0] + results["dk"][0]
     fused = results["dkv fused"][0]
     bwd_flops = 2.5 * 2 * unit
