@@ -215,7 +215,8 @@ int magi_grpcoll_pull(const struct magi_grpcoll_pull_args* args);
  * index_attn_indices direct-to-kernel path (flex_flash_attn.py:1358-1390).
  * indices_2d[i] lists the GLOBAL K rows attended by q token row i, shared
  * by all hq query heads of that row; -1 = contiguous tail padding. KV heads
- * are folded into the K row dimension (hk must be 1). Forward only. */
+ * are folded into the K row dimension (hk must be 1). The reference is
+ * forward-only here; magi_ffa_bwd_index below adds the backward. */
 typedef struct magi_ffa_index_args {
   const void* q;              /* bf16 [total_q, hq, d] */
   const void* k;              /* bf16 [total_k, 1, d] */
@@ -236,6 +237,40 @@ typedef struct magi_ffa_index_args {
 } magi_ffa_index_args;
 
 int magi_ffa_fwd_index(const magi_ffa_index_args* args);
+
+/* Index-attention backward (beyond the reference, whose autograd returns None
+ * for index_attn): gathers K/V rows as the forward does, keeps dQ in
+ * registers (single owner, stored once as bf16) and scatters dK/dV with fp32
+ * atomic adds at row indices_2d[i][j] - padding and out-of-range slots issue
+ * no atomic. Not deterministic (fp32 atomics reorder). dpsum must hold
+ * rowsum(dO * O): run magi_ffa_bwd_preprocess first (it reads only
+ * dout/out/dpsum/total_q/hq/d/out_is_fp32/stream of magi_ffa_bwd_args).
+ * Validation codes mirror magi_ffa_fwd_index: -1 null pointer, -2 d not in
+ * {64, 128}, -3 hk != 1, -4 max_topk not a positive multiple of 64;
+ * total_q <= 0 returns 0 without a launch. */
+typedef struct magi_ffa_index_bwd_args {
+  const void* dout;           /* bf16 [total_q, hq, d] */
+  const void* q;              /* bf16 [total_q, hq, d] */
+  const void* k;              /* bf16 [total_k, 1, d] */
+  const void* v;              /* bf16 [total_k, 1, d] */
+  const float* lse;           /* f32 [total_q, hq] (forward output) */
+  const float* dpsum;         /* f32 [total_q, hq] = rowsum(dO * O) */
+  const int32_t* indices_2d;  /* [total_q, max_topk] global K row ids, -1 pad */
+  void* dq;                   /* bf16 [total_q, hq, d], zero-init, plain stores */
+  float* dk;                  /* f32 [total_k, 1, d], zeroed, atomic-accumulated */
+  float* dv;                  /* f32 [total_k, 1, d], zeroed, atomic-accumulated */
+  int64_t total_q;
+  int64_t total_k;
+  int32_t max_topk;           /* multiple of 64 */
+  int32_t hq;
+  int32_t hk;                 /* must be 1 */
+  int32_t d;                  /* 64 or 128 */
+  float softmax_scale;
+  float softcap;
+  void* stream;               /* hipStream_t */
+} magi_ffa_index_bwd_args;
+
+int magi_ffa_bwd_index(const magi_ffa_index_bwd_args* args);
 
 /* Version/identity probe so tests can verify the native library is loaded. */
 int magi_ffa_abi_version(void);

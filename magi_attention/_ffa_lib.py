@@ -154,6 +154,32 @@ class MagiFfaIndexArgs(ctypes.Structure):
     ]
 
 
+class MagiFfaIndexBwdArgs(ctypes.Structure):
+    """mirrors magi_ffa_index_bwd_args (index-attention backward)"""
+
+    _fields_ = [
+        ("dout", ctypes.c_void_p),
+        ("q", ctypes.c_void_p),
+        ("k", ctypes.c_void_p),
+        ("v", ctypes.c_void_p),
+        ("lse", ctypes.c_void_p),
+        ("dpsum", ctypes.c_void_p),
+        ("indices_2d", ctypes.c_void_p),
+        ("dq", ctypes.c_void_p),
+        ("dk", ctypes.c_void_p),
+        ("dv", ctypes.c_void_p),
+        ("total_q", ctypes.c_int64),
+        ("total_k", ctypes.c_int64),
+        ("max_topk", ctypes.c_int32),
+        ("hq", ctypes.c_int32),
+        ("hk", ctypes.c_int32),
+        ("d", ctypes.c_int32),
+        ("softmax_scale", ctypes.c_float),
+        ("softcap", ctypes.c_float),
+        ("stream", ctypes.c_void_p),
+    ]
+
+
 class MagiCorrectArgs(ctypes.Structure):
     _fields_ = [
         ("out1", ctypes.c_void_p),
@@ -177,6 +203,7 @@ def _try_load() -> ctypes.CDLL | None:
             ("magi_ffa_fwd", [ctypes.POINTER(MagiFfaFwdArgs)]),
             ("magi_ffa_fwd_fp8", [ctypes.POINTER(MagiFfaFwdArgs)]),
             ("magi_ffa_fwd_index", [ctypes.POINTER(MagiFfaIndexArgs)]),
+            ("magi_ffa_bwd_index", [ctypes.POINTER(MagiFfaIndexBwdArgs)]),
             ("magi_ffa_bwd", [ctypes.POINTER(MagiFfaBwdArgs)]),
             ("magi_ffa_bwd_dq", [ctypes.POINTER(MagiFfaBwdArgs)]),
             ("magi_ffa_bwd_dkv", [ctypes.POINTER(MagiFfaBwdArgs)]),

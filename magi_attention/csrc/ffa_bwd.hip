@@ -40,32 +40,6 @@
 
 DEV_INLINE bool wave_alive(int m0, int qe) { return m0 < qe; }
 
-DEV_INLINE bf16x8 cframe_to_afrag(const float* val, int tt) {
-  unsigned c0 = pack_bf16_pair(val[8 * tt + 0], val[8 * tt + 1]);
-  unsigned c1 = pack_bf16_pair(val[8 * tt + 2], val[8 * tt + 3]);
-  unsigned c2 = pack_bf16_pair(val[8 * tt + 4], val[8 * tt + 5]);
-  unsigned c3 = pack_bf16_pair(val[8 * tt + 6], val[8 * tt + 7]);
-  {
-    auto r2 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
-    c0 = r2[0];
-    c2 = r2[1];
-  }
-  {
-    auto r2 = __builtin_amdgcn_permlane32_swap(c1, c3, false, false);
-    c1 = r2[0];
-    c3 = r2[1];
-  }
-  union {
-    unsigned u[4];
-    bf16x8 v;
-  } cvt;
-  cvt.u[0] = c0;
-  cvt.u[1] = c1;
-  cvt.u[2] = c2;
-  cvt.u[3] = c3;
-  return cvt.v;
-}
-
 struct BwdParams {
   const bf16_t* dout;
   const bf16_t* q;

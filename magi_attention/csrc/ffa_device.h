@@ -1,7 +1,8 @@
 // ffa_device.h — device helpers shared by the FFA kernels (gfx950, wave64):
 // vector typedefs, the software-pipelined LDS-DMA barrier, and the MFMA
 // 32x32x16 fragment helpers. Included by ffa_fwd.hip, ffa_bwd.hip,
-// ffa_index.hip and ffa_fwd_fp8.hip; everything here is force-inlined.
+// ffa_index.hip, ffa_index_bwd.hip and ffa_fwd_fp8.hip; everything here is
+// force-inlined.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -69,4 +70,33 @@ DEV_INLINE bf16x8 tr16_frag(int a0, int a1) {
   r.h[0] = v0;
   r.h[1] = v1;
   return r.v;
+}
+
+// Half (tt = 0/1) of a 32x32 C/D fragment (16 fp32 per lane) -> bf16 MFMA
+// A-fragment of the same matrix: packed converts + two permlane32 swaps,
+// no LDS round trip.
+DEV_INLINE bf16x8 cframe_to_afrag(const float* val, int tt) {
+  unsigned c0 = pack_bf16_pair(val[8 * tt + 0], val[8 * tt + 1]);
+  unsigned c1 = pack_bf16_pair(val[8 * tt + 2], val[8 * tt + 3]);
+  unsigned c2 = pack_bf16_pair(val[8 * tt + 4], val[8 * tt + 5]);
+  unsigned c3 = pack_bf16_pair(val[8 * tt + 6], val[8 * tt + 7]);
+  {
+    auto r2 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
+    c0 = r2[0];
+    c2 = r2[1];
+  }
+  {
+    auto r2 = __builtin_amdgcn_permlane32_swap(c1, c3, false, false);
+    c1 = r2[0];
+    c3 = r2[1];
+  }
+  union {
+    unsigned u[4];
+    bf16x8 v;
+  } cvt;
+  cvt.u[0] = c0;
+  cvt.u[1] = c1;
+  cvt.u[2] = c2;
+  cvt.u[3] = c3;
+  return cvt.v;
 }

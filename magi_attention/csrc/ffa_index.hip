@@ -8,8 +8,9 @@
 //   - KV heads are folded into the K row dimension (hk == 1): global id for
 //     (batch b, token t, kv-head h) is (b*S_kv + t)*NHK + h
 //     (utils/sparse_utils.py:534-574).
-//   - forward only (reference backward receives None for index_attn,
-//     flex_flash_attn.py:950-954).
+//   - this file is the forward; the reference stops there (its backward
+//     receives None for index_attn, flex_flash_attn.py:950-954). The
+//     gather/scatter backward lives in ffa_index_bwd.hip.
 //
 // MI355X mapping (NOT the reference's SM90 kBlockM/PackGQA scheme): the MFMA
 // M dimension is the token's hq query heads — the reference's PackGQA is the

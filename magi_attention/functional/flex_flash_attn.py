@@ -362,7 +362,8 @@ def _flex_flash_attn_forward_index(
     index_attn_indices direct-to-kernel path (flex_flash_attn.py:1358-1390).
     indices_2d [total_q, max_topk] int32 lists the GLOBAL K rows each q token
     row attends, shared by all hq query heads; -1 = contiguous tail padding.
-    Forward only (the reference backward receives None for index_attn)."""
+    This is the forward pass; _flex_flash_attn_backward_index differentiates
+    it (the reference backward receives None for index_attn)."""
     from .._ffa_lib import MagiFfaIndexArgs
 
     assert q.dtype == torch.bfloat16, "index_attn requires bf16 inputs"
@@ -392,6 +393,91 @@ def _flex_flash_attn_forward_index(
     )
     check(_ffa_lib.lib().magi_ffa_fwd_index(args), "magi_ffa_fwd_index")
     return out, AttnForwardMeta(lse=lse, max_logits=None)
+
+
+def _flex_flash_attn_backward_index(
+    dout: torch.Tensor,
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    out: torch.Tensor,
+    lse: torch.Tensor,
+    indices_2d: torch.Tensor,
+    softmax_scale: float,
+    softcap: float,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Index-attention backward (csrc/ffa_index_bwd.hip): dpsum preprocess,
+    then one gather/scatter kernel. Returns (dq bf16, dk fp32, dv fp32): dq has
+    a single owner per row and is stored directly; dk/dv are fp32 accumulators
+    the kernel scatters into with atomic adds (not deterministic)."""
+    from .._ffa_lib import MagiFfaIndexBwdArgs
+
+    assert q.dtype == torch.bfloat16, "index_attn requires bf16 inputs"
+    dout, q, k, v, out, lse, indices_2d = [
+        maybe_contiguous(x) for x in (dout, q, k, v, out, lse, indices_2d)
+    ]
+    if dout.dtype != q.dtype:
+        dout = dout.to(q.dtype)
+    tq, hq, d = q.shape
+    tk, hk, _ = k.shape
+    max_topk = indices_2d.shape[1]
+
+    dq = torch.zeros_like(q)
+    dk = torch.zeros_like(k, dtype=torch.float32)
+    dv = torch.zeros_like(v, dtype=torch.float32)
+    dpsum = torch.empty(tq, hq, dtype=torch.float32, device=q.device)
+
+    lib = _ffa_lib.lib()
+    pre = MagiFfaBwdArgs(
+        dout=ptr(dout), out=ptr(out), dpsum=ptr(dpsum),
+        total_q=tq, hq=hq, d=d,
+        out_is_fp32=int(out.dtype == torch.float32),
+        stream=current_stream_ptr(),
+    )
+    check(lib.magi_ffa_bwd_preprocess(pre), "magi_ffa_bwd_preprocess")
+    args = MagiFfaIndexBwdArgs(
+        dout=ptr(dout), q=ptr(q), k=ptr(k), v=ptr(v), lse=ptr(lse),
+        dpsum=ptr(dpsum), indices_2d=ptr(indices_2d),
+        dq=ptr(dq), dk=ptr(dk), dv=ptr(dv),
+        total_q=tq, total_k=tk, max_topk=max_topk,
+        hq=hq, hk=hk, d=d,
+        softmax_scale=softmax_scale, softcap=softcap,
+        stream=current_stream_ptr(),
+    )
+    check(lib.magi_ffa_bwd_index(args), "magi_ffa_bwd_index")
+    return dq, dk, dv
+
+
+class IndexAttnFunc(torch.autograd.Function):
+    """Differentiable index attention: forward = the gather kernel, backward =
+    preprocess + the gather/scatter kernel. The index tensor and the scalar
+    arguments get no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, indices_2d, softmax_scale, softcap):
+        out, meta = _flex_flash_attn_forward_index(
+            q, k, v, indices_2d, softmax_scale, softcap
+        )
+        ctx.save_for_backward(q, k, v, out, meta.lse, indices_2d)
+        ctx.softmax_scale = softmax_scale
+        ctx.softcap = softcap
+        ctx.mark_non_differentiable(meta.lse)
+        return out, meta.lse
+
+    @staticmethod
+    def backward(ctx, dout, _dlse):
+        q, k, v, out, lse, indices_2d = ctx.saved_tensors
+        dq, dk, dv = _flex_flash_attn_backward_index(
+            dout, q, k, v, out, lse, indices_2d,
+            ctx.softmax_scale, ctx.softcap,
+        )
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        return (
+            dq if need_q else None,
+            dk.to(k.dtype) if need_k else None,
+            dv.to(v.dtype) if need_v else None,
+            None, None, None,
+        )
 
 
 def _flex_flash_attn_backward(
@@ -633,7 +719,9 @@ def flex_flash_attn_func(
     max_topk) int32 GLOBAL K row ids, -1 tail padding, mutually exclusive
     with q_ranges/k_ranges; max_topk must be a multiple of 64 (the MI355X
     staged-tile size; the reference requires 128, so any reference-legal
-    input is accepted). Forward only."""
+    input is accepted). Differentiable in q, k and v on the GPU (the
+    reference is forward-only here): dK/dV are scattered with fp32 atomic
+    adds, so deterministic=True is rejected when a gradient is needed."""
     # ── sparse-input validation (mirrors reference :1344-1384) ──
     _has_ranges = q_ranges is not None
     _has_index = index_attn_indices is not None
@@ -658,31 +746,50 @@ def flex_flash_attn_func(
             f"index_attn max_topk={max_topk} must be a multiple of 64 "
             f"(pad with -1)"
         )
-        assert not (
-            torch.is_grad_enabled()
-            and any(t.requires_grad for t in (q, k, v))
-        ), "index_attn is forward-only (matches the reference)"
+        # the differentiable path is taken only when a gradient can flow; the
+        # no-grad call below is the plain forward launch
+        needs_grad = torch.is_grad_enabled() and any(
+            t.requires_grad for t in (q, k, v)
+        )
+        if needs_grad:
+            assert q.is_cuda and k.is_cuda and v.is_cuda, (
+                "index_attn backward needs GPU tensors (the gather/scatter "
+                "kernel takes device pointers only)"
+            )
+            assert not deterministic, (
+                "index_attn backward has no deterministic mode: dK/dV are "
+                "scattered with fp32 atomic adds, whose order is not fixed; "
+                "pass deterministic=False"
+            )
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
+        indices_2d = index_attn_indices.reshape(-1, max_topk)
+
+        def _index_call(q_, k_, v_):
+            if needs_grad:
+                out_, lse_ = IndexAttnFunc.apply(
+                    q_, k_, v_, indices_2d, softmax_scale, softcap
+                )
+                return out_, AttnForwardMeta(lse=lse_, max_logits=None)
+            return _flex_flash_attn_forward_index(
+                q_, k_, v_, indices_2d, softmax_scale, softcap
+            )
+
         d = q.shape[-1]
         if d not in (64, 128):
             # zero-pad odd head dims into the next bucket (same scheme as the
-            # dense path below; exact for attention)
+            # dense path below; exact for attention, and autograd slices the
+            # gradients back through the pad)
             assert d < 128, f"index_attn head_dim {d} > 128 unsupported"
             bucket = 64 if d <= 64 else 128
             pad = bucket - d
-            out, meta = _flex_flash_attn_forward_index(
+            out, meta = _index_call(
                 torch.nn.functional.pad(q, (0, pad)),
                 torch.nn.functional.pad(k, (0, pad)),
                 torch.nn.functional.pad(v, (0, pad)),
-                index_attn_indices.reshape(-1, max_topk),
-                softmax_scale, softcap,
             )
             return out[..., :d], meta
-        return _flex_flash_attn_forward_index(
-            q, k, v, index_attn_indices.reshape(-1, max_topk),
-            softmax_scale, softcap,
-        )
+        return _index_call(q, k, v)
     d = q.shape[-1]
     if d not in (64, 128, 192):
         # arbitrary head dims run in the next bucket with zero feature
