@@ -238,6 +238,18 @@ typedef struct magi_ffa_index_args {
 
 int magi_ffa_fwd_index(const magi_ffa_index_args* args);
 
+/* fp8 (OCP e4m3) index-attention forward (csrc/ffa_index_fp8.hip). Same args
+ * struct, but for this entry q, k and v hold raw e4m3 BYTES (1 byte per
+ * element, rows of d bytes, no descale factors); out is bf16 (or f32 with
+ * out_is_fp32) and lse f32, zero / -inf initialised by the caller as above.
+ * Numerics are the fp8 convention of magi_ffa_fwd_fp8 (P in [0, 256] packed
+ * to e4m3, fp32 accumulate); softcap is supported. Validation order and
+ * codes are those of magi_ffa_fwd_index, all returned before any HIP call:
+ * -1 null pointer, -2 d not in {64, 128}, -3 hk != 1, -4 max_topk not a
+ * positive multiple of 64; total_q <= 0 or hq <= 0 returns 0 without a
+ * launch. */
+int magi_ffa_fwd_index_fp8(const magi_ffa_index_args* args);
+
 /* Index-attention backward (beyond the reference, whose autograd returns None
  * for index_attn): gathers K/V rows as the forward does, keeps dQ in
  * registers (single owner, stored once as bf16) and scatters dK/dV with fp32

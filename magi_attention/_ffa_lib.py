@@ -203,6 +203,7 @@ def _try_load() -> ctypes.CDLL | None:
             ("magi_ffa_fwd", [ctypes.POINTER(MagiFfaFwdArgs)]),
             ("magi_ffa_fwd_fp8", [ctypes.POINTER(MagiFfaFwdArgs)]),
             ("magi_ffa_fwd_index", [ctypes.POINTER(MagiFfaIndexArgs)]),
+            ("magi_ffa_fwd_index_fp8", [ctypes.POINTER(MagiFfaIndexArgs)]),
             ("magi_ffa_bwd_index", [ctypes.POINTER(MagiFfaIndexBwdArgs)]),
             ("magi_ffa_bwd", [ctypes.POINTER(MagiFfaBwdArgs)]),
             ("magi_ffa_bwd_dq", [ctypes.POINTER(MagiFfaBwdArgs)]),

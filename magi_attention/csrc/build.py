@@ -22,6 +22,7 @@ SOURCES = [
     CSRC / "ffa_fwd.hip",
     CSRC / "ffa_index.hip",
     CSRC / "ffa_index_bwd.hip",
+    CSRC / "ffa_index_fp8.hip",
     CSRC / "ffa_bwd.hip",
     CSRC / "range_ops.hip",
     CSRC / "ffa_fwd_fp8.hip",

@@ -1,8 +1,8 @@
 // ffa_device.h — device helpers shared by the FFA kernels (gfx950, wave64):
 // vector typedefs, the software-pipelined LDS-DMA barrier, and the MFMA
 // 32x32x16 fragment helpers. Included by ffa_fwd.hip, ffa_bwd.hip,
-// ffa_index.hip, ffa_index_bwd.hip and ffa_fwd_fp8.hip; everything here is
-// force-inlined.
+// ffa_index.hip, ffa_index_bwd.hip, ffa_fwd_fp8.hip and ffa_index_fp8.hip;
+// everything here is force-inlined.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -99,4 +99,32 @@ DEV_INLINE bf16x8 cframe_to_afrag(const float* val, int tt) {
   cvt.u[2] = c2;
   cvt.u[3] = c3;
   return cvt.v;
+}
+
+// ---- fp8 (OCP e4m3) helpers shared by ffa_fwd_fp8.hip / ffa_index_fp8.hip ----
+
+// f32 -> e4m3 via the packed convert (lower byte)
+DEV_INLINE unsigned char to_fp8(float x) {
+  union {
+    short s;
+    unsigned char b[2];
+  } r;
+  r.s = __builtin_amdgcn_cvt_pk_fp8_f32(x, 0.f, 0, false);
+  return r.b[0];
+}
+
+// Half (tt = 0/1) of a 32x32 C/D fragment -> fp8 MFMA A-fragment (8 e4m3
+// bytes) of the same matrix: pack 4 + 4 bytes, ONE permlane32 swap per 16-k.
+DEV_INLINE long cframe_to_afrag_fp8(const float* val, int tt) {
+  union {
+    unsigned char b[4];
+    unsigned u;
+  } A, B;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    A.b[j] = to_fp8(val[8 * tt + j]);
+    B.b[j] = to_fp8(val[8 * tt + 4 + j]);
+  }
+  auto r2 = __builtin_amdgcn_permlane32_swap(A.u, B.u, false, false);
+  return ((long)(unsigned)r2[1] << 32) | (unsigned)r2[0];
 }

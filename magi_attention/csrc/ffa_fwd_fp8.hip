@@ -30,16 +30,6 @@
 
 using u8 = unsigned char;
 
-DEV_INLINE u8 to_fp8(float x) {
-  // f32 -> e4m3 via the packed convert (lower byte)
-  union {
-    short s;
-    u8 b[2];
-  } r;
-  r.s = __builtin_amdgcn_cvt_pk_fp8_f32(x, 0.f, 0, false);
-  return r.b[0];
-}
-
 struct Fp8FwdParams {
   const u8* q;
   const u8* k;
@@ -253,19 +243,7 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
     // ---- P -> fp8 A-fragments (pack 4 + ONE permlane swap per 16-k) ----
     long pa[2];
 #pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-      union {
-        u8 b[4];
-        unsigned u;
-      } A, B;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        A.b[j] = to_fp8(pr[8 * tt + j]);
-        B.b[j] = to_fp8(pr[8 * tt + 4 + j]);
-      }
-      auto r2 = __builtin_amdgcn_permlane32_swap(A.u, B.u, false, false);
-      pa[tt] = ((long)(unsigned)r2[1] << 32) | (unsigned)r2[0];
-    }
+    for (int tt = 0; tt < 2; ++tt) pa[tt] = cframe_to_afrag_fp8(pr, tt);
 
     // ---- PV from the byte-transposed V tile ----
 #pragma unroll

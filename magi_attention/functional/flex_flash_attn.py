@@ -363,10 +363,19 @@ def _flex_flash_attn_forward_index(
     indices_2d [total_q, max_topk] int32 lists the GLOBAL K rows each q token
     row attends, shared by all hq query heads; -1 = contiguous tail padding.
     This is the forward pass; _flex_flash_attn_backward_index differentiates
-    it (the reference backward receives None for index_attn)."""
+    it (the reference backward receives None for index_attn).
+
+    q/k/v are all bf16 (csrc/ffa_index.hip) or all fp8-e4m3
+    (csrc/ffa_index_fp8.hip: raw e4m3 bytes, no descale factors, the fp8
+    softmax convention of the dense fp8 forward); out is bf16 either way."""
     from .._ffa_lib import MagiFfaIndexArgs
 
-    assert q.dtype == torch.bfloat16, "index_attn requires bf16 inputs"
+    is_fp8 = q.dtype == torch.float8_e4m3fn
+    assert q.dtype == torch.bfloat16 or is_fp8, "index_attn requires bf16 inputs"
+    assert k.dtype == q.dtype and v.dtype == q.dtype, (
+        "index_attn q, k and v must all be fp8-e4m3 or all be bf16, got "
+        f"q={q.dtype}, k={k.dtype}, v={v.dtype}"
+    )
     q, k, v, indices_2d = [maybe_contiguous(x) for x in (q, k, v, indices_2d)]
     tq, hq, d = q.shape
     tk, hk, _ = k.shape
@@ -380,7 +389,7 @@ def _flex_flash_attn_forward_index(
     )
     max_topk = indices_2d.shape[1]
 
-    out = torch.zeros(tq, hq, d, dtype=q.dtype, device=q.device)
+    out = torch.zeros(tq, hq, d, dtype=torch.bfloat16, device=q.device)
     lse = torch.full((tq, hq), float("-inf"), dtype=torch.float32, device=q.device)
 
     args = MagiFfaIndexArgs(
@@ -391,8 +400,32 @@ def _flex_flash_attn_forward_index(
         softmax_scale=softmax_scale, softcap=softcap,
         out_is_fp32=0, stream=current_stream_ptr(),
     )
-    check(_ffa_lib.lib().magi_ffa_fwd_index(args), "magi_ffa_fwd_index")
+    if is_fp8:
+        check(_ffa_lib.lib().magi_ffa_fwd_index_fp8(args),
+              "magi_ffa_fwd_index_fp8")
+    else:
+        check(_ffa_lib.lib().magi_ffa_fwd_index(args), "magi_ffa_fwd_index")
     return out, AttnForwardMeta(lse=lse, max_logits=None)
+
+
+def _index_head_dim_pad(d: int) -> int:
+    """zero columns that take head dim d to its kernel bucket (64 or 128)"""
+    if d in (64, 128):
+        return 0
+    assert d < 128, f"index_attn head_dim {d} > 128 unsupported"
+    return (64 if d <= 64 else 128) - d
+
+
+def _pad_head_dim(t: torch.Tensor, pad: int) -> torch.Tensor:
+    """Zero-pad the last dim. fp8 goes through a uint8 view (constant pad is
+    not implemented for fp8 on every backend; zero bytes are e4m3 +0)."""
+    if pad == 0:
+        return t
+    if t.dtype == torch.float8_e4m3fn:
+        return torch.nn.functional.pad(
+            t.contiguous().view(torch.uint8), (0, pad)
+        ).view(torch.float8_e4m3fn)
+    return torch.nn.functional.pad(t, (0, pad))
 
 
 def _flex_flash_attn_backward_index(
@@ -451,31 +484,49 @@ def _flex_flash_attn_backward_index(
 class IndexAttnFunc(torch.autograd.Function):
     """Differentiable index attention: forward = the gather kernel, backward =
     preprocess + the gather/scatter kernel. The index tensor and the scalar
-    arguments get no gradient."""
+    arguments get no gradient.
+
+    fp8-e4m3 inputs run the fp8 forward kernel; their backward runs the bf16
+    kernels over upcast operands with the fp8 forward's out/lse, and the
+    gradients are cast back to fp8 (the policy of FlexFlashAttnFunc.backward).
+    An odd fp8 head dim is zero-padded here, not by the caller: the forward
+    pads the bytes and the backward pads the bf16 upcast."""
 
     @staticmethod
     def forward(ctx, q, k, v, indices_2d, softmax_scale, softcap):
+        is_fp8 = q.dtype == torch.float8_e4m3fn
+        d = q.shape[-1]
+        pad = _index_head_dim_pad(d) if is_fp8 else 0
         out, meta = _flex_flash_attn_forward_index(
-            q, k, v, indices_2d, softmax_scale, softcap
+            _pad_head_dim(q, pad), _pad_head_dim(k, pad), _pad_head_dim(v, pad),
+            indices_2d, softmax_scale, softcap,
         )
         ctx.save_for_backward(q, k, v, out, meta.lse, indices_2d)
         ctx.softmax_scale = softmax_scale
         ctx.softcap = softcap
+        ctx.pad = pad
         ctx.mark_non_differentiable(meta.lse)
-        return out, meta.lse
+        return (out[..., :d] if pad else out), meta.lse
 
     @staticmethod
     def backward(ctx, dout, _dlse):
         q, k, v, out, lse, indices_2d = ctx.saved_tensors
+        in_dtype = q.dtype
+        d = q.shape[-1]
+        if in_dtype == torch.float8_e4m3fn:
+            pad = ctx.pad
+            q, k, v, dout = [
+                _pad_head_dim(t.to(torch.bfloat16), pad) for t in (q, k, v, dout)
+            ]
         dq, dk, dv = _flex_flash_attn_backward_index(
             dout, q, k, v, out, lse, indices_2d,
             ctx.softmax_scale, ctx.softcap,
         )
         need_q, need_k, need_v = ctx.needs_input_grad[:3]
         return (
-            dq if need_q else None,
-            dk.to(k.dtype) if need_k else None,
-            dv.to(v.dtype) if need_v else None,
+            dq[..., :d].to(in_dtype) if need_q else None,
+            dk[..., :d].to(in_dtype) if need_k else None,
+            dv[..., :d].to(in_dtype) if need_v else None,
             None, None, None,
         )
 
@@ -721,7 +772,9 @@ def flex_flash_attn_func(
     staged-tile size; the reference requires 128, so any reference-legal
     input is accepted). Differentiable in q, k and v on the GPU (the
     reference is forward-only here): dK/dV are scattered with fp32 atomic
-    adds, so deterministic=True is rejected when a gradient is needed."""
+    adds, so deterministic=True is rejected when a gradient is needed.
+    q/k/v may be all bf16 or all float8_e4m3fn (fp8 forward kernel, bf16 out,
+    bf16-upcast backward, fp8 gradients)."""
     # ── sparse-input validation (mirrors reference :1344-1384) ──
     _has_ranges = q_ranges is not None
     _has_index = index_attn_indices is not None
@@ -780,13 +833,14 @@ def flex_flash_attn_func(
             # zero-pad odd head dims into the next bucket (same scheme as the
             # dense path below; exact for attention, and autograd slices the
             # gradients back through the pad)
-            assert d < 128, f"index_attn head_dim {d} > 128 unsupported"
-            bucket = 64 if d <= 64 else 128
-            pad = bucket - d
+            pad = _index_head_dim_pad(d)
+            if needs_grad and q.dtype == torch.float8_e4m3fn:
+                # fp8 under autograd: IndexAttnFunc pads inside (a byte-view
+                # pad is not differentiable)
+                return _index_call(q, k, v)
             out, meta = _index_call(
-                torch.nn.functional.pad(q, (0, pad)),
-                torch.nn.functional.pad(k, (0, pad)),
-                torch.nn.functional.pad(v, (0, pad)),
+                _pad_head_dim(q, pad), _pad_head_dim(k, pad),
+                _pad_head_dim(v, pad),
             )
             return out[..., :d], meta
         return _index_call(q, k, v)
