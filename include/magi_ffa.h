@@ -123,7 +123,9 @@ typedef struct magi_range_op_args {
   int64_t n_ranges;
   int64_t row_elems;        /* elements per row (h*d) */
   int64_t total_rows;       /* total rows moved (sum of range lengths) */
-  int32_t elem_size;        /* bytes per element: 2 (bf16) or 4 (f32) */
+  int32_t elem_size;        /* bytes per element: 1 (fp8/u8), 2 (bf16) or 4 (f32);
+                               copies take any row byte count, sum needs f32 rows
+                               of a multiple of 16 bytes (else rc -2) */
   int32_t n_heads;          /* for lse variant: row_elems = n_heads*d */
   int32_t reduce_op;        /* 0=copy(gather/scatter), 1=sum, 2=lse-weighted */
   void* stream;
