@@ -247,6 +247,12 @@ def _flex_flash_attn_forward(
     assert q.dtype in (torch.bfloat16, torch.float8_e4m3fn), (
         "bf16 or fp8-e4m3 inputs"
     )
+    # the kernel is picked from q.dtype alone and reads k and v at q's
+    # element size: a mixed call would run past the end of the narrower buffers
+    assert k.dtype == q.dtype and v.dtype == q.dtype, (
+        "flex_flash_attn q, k and v must all be fp8-e4m3 or all be bf16, got "
+        f"q={q.dtype}, k={k.dtype}, v={v.dtype}"
+    )
     q, k, v, q_ranges, k_ranges = [
         maybe_contiguous(x) for x in (q, k, v, q_ranges, k_ranges)
     ]
