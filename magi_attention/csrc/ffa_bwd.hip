@@ -24,6 +24,14 @@
 //                                      B-frags by tr16 reads)
 //     MODE 0 computes both (fused: K and V tiles live in LDS), MODE 1 only dV,
 //     MODE 2 only dK (split: K/V fragments live in registers).
+//     lse / dpsum of the staged q rows: the split modes stage them into LDS
+//     by LDS-DMA next to the Q/dO image. The fused mode has no LDS left for
+//     them: each lane loads the lse and dpsum of one row per 32-row subtile
+//     into registers, one staged tile AHEAD and before that tile's prefetch,
+//     and compute selects rows with ds_bpermute. The fused mode also issues
+//     its Q/dO prefetch outside the compiler's waitcnt tracking
+//     (glds16_untracked), so its subtile loop holds no vector-memory wait and
+//     the prefetch flies for the whole iteration.
 // 8 waves (one 512-thread workgroup per CU, 2 waves/SIMD) serve long ranges,
 // 4 waves short ranges and D=192; the launchers at the end of the file pick.
 // The staging ring depth (NBUF) is fixed by (MODE, WAVES) inside each kernel.
@@ -39,6 +47,22 @@
 #define BWD_BM 32    // q rows per tile
 
 DEV_INLINE bool wave_alive(int m0, int qe) { return m0 < qe; }
+
+// 16-byte-per-lane LDS-DMA (global_load_lds_dwordx4) issued from inline asm,
+// so the compiler's waitcnt pass does not track it. The builtin form leaves a
+// "pending LDS write" on the VM counter in that pass, and it then puts
+// `s_waitcnt vmcnt(0)` in front of the first ds_read_b64_tr_b16 that follows
+// (the tr16 builtin is not marked read-only, so it is ordered against the
+// DMA) — in a prefetch pipeline that drains the next tile's DMA in the
+// middle of the compute phase meant to cover it. Callers own the ordering:
+// the staged image may only be read after a pipe_barrier that retires it.
+// lds_byte is the wave-uniform LDS byte address of the destination; lane l
+// lands at lds_byte + 16 * l.
+DEV_INLINE void glds16_untracked(const void* gsrc, int lds_byte) {
+  const int m0v = __builtin_amdgcn_readfirstlane(lds_byte);
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
+               :: "s"(m0v), "v"(gsrc) : "memory", "m0");
+}
 
 struct BwdParams {
   const bf16_t* dout;
@@ -243,10 +267,11 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   // budget).
   const int krow = n0 + lo32;
   const int kcl = min(krow, ke - 1);
-  // MODE 0 does NOT keep K fragments live across the q loop: the lane re-reads
-  // its own K row per subtile (8 b128 loads, L1/L2-resident) so the registers
-  // are subtile-local — keeping them loop-live was exactly what pushed the
-  // fused kernel to 437 regs / scratch spills.
+  // MODE 0 does NOT keep K fragments live across the q loop — that was what
+  // pushed the first fused kernel to 437 regs / scratch spills. It reads no K
+  // from global memory in the loop either: each subtile takes its K (and V)
+  // fragments off the wave's LDS tile staged below, so the registers are
+  // subtile-local. kp_row serves the split modes only.
   const bf16_t* kp_row = p.k + (size_t)kcl * k_pitch + (size_t)kh * D + hi * 8;
   bf16x8 kfA[V_IN_LDS ? 1 : DF], vfA[(WANT_DK && !V_IN_LDS) ? DF : 1];
   if constexpr (!V_IN_LDS) {
@@ -311,6 +336,11 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   static_assert(NBUF == 2 || GLDS_TOTAL % WAVES == 0, "uniform stage count");
   constexpr int GLDS_PER_WAVE =
       (GLDS_TOTAL % WAVES == 0) ? GLDS_TOTAL / WAVES : 0;  // 0 = non-uniform
+  // block-uniform operands of the staging addresses (scalar registers)
+  const bf16_t* q_head = p.q + (size_t)h * D;
+  const bf16_t* do_head = p.dout + (size_t)h * D;
+  const int smem_byte = (int)(unsigned long long)(
+      (__attribute__((address_space(3))) const char*)smem);
   auto stage_glds = [&](int buf, int m0x) {
 #pragma unroll
     for (int gi0 = 0; gi0 < (GLDS_TOTAL + WAVES - 1) / WAVES; ++gi0) {
@@ -323,14 +353,28 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
       int cs = c ^ ((r & SW32M) << 1);
       if (cs >= VSLOTS) cs = 0;
       const int csw = cs * 8;
+      // ONE per-lane element offset for both tensors, added to the
+      // block-uniform head pointers: written as p.q + row + (head, slot) the
+      // compiler hoists a per-lane 64-bit pointer per tensor out of the q
+      // loop, and at the fused kernel's register cap spills them — each
+      // reload's vmcnt(0) then serialises the loads issued here
+      const size_t eoff = (size_t)qrow * q_pitch + (unsigned)csw;
+      if constexpr (V_IN_LDS) {
+        // fused mode: keep the prefetch out of the compiler's waitcnt
+        // bookkeeping (see glds16_untracked) — every read of a staged
+        // image already sits behind the pipe_barrier that retires it
+        const int lq = smem_byte + (2 * buf * QITER + r0) * ROWB;
+        glds16_untracked(q_head + eoff, lq);
+        glds16_untracked(do_head + eoff, lq + QITER * ROWB);
+        continue;
+      }
       __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(
-              p.q + (size_t)qrow * q_pitch + (size_t)h * D + csw),
+          (const __attribute__((address_space(1))) unsigned int*)(q_head + eoff),
           (__attribute__((address_space(3))) unsigned int*)&lds_q(buf)[r0 * ROWE],
           16, 0, 0);
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) unsigned int*)(
-              p.dout + (size_t)qrow * q_pitch + (size_t)h * D + csw),
+              do_head + eoff),
           (__attribute__((address_space(3))) unsigned int*)&lds_do(buf)[r0 * ROWE],
           16, 0, 0);
     }
@@ -355,6 +399,28 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   // vm ops per stage call per wave (glds pairs + lse groups) — the NBUF=3
   // constant-distance barrier counts on EVERY stage issuing exactly this many
   constexpr int GOPS = 2 * GLDS_PER_WAVE + 2;
+  // MODE 0 has no LDS room for lse/dpsum: lane l holds the lse and the dpsum
+  // of row (l & 31) of each 32-row subtile and compute cross-lane-selects
+  // with ds_bpermute (both through the same row index; both halves of the
+  // wave load the same 32 rows from the uniform base pointers, which costs
+  // no per-lane pointer register). The values are register-prefetched ONE
+  // staged tile ahead, issued BEFORE that tile's stage_glds: vector-memory
+  // loads retire in order, so a load issued after the prefetch could only be
+  // awaited with vmcnt(0), which also waits out the whole Q/dO prefetch in
+  // the middle of the compute phase it was meant to hide under. Issued one
+  // tile early, the values land by the next pipe_barrier<0> and the subtile
+  // loop contains no vector-memory wait. Rows clamp to qe-1 like the staged
+  // rows; nothing is carried across a q segment.
+  float lse_nxt[V_IN_LDS ? NSUB : 1] = {}, dps_nxt[V_IN_LDS ? NSUB : 1] = {};
+  auto load_lsedp = [&](int m0x) {
+#pragma unroll
+    for (int sg = 0; sg < NSUB; ++sg) {
+      const int qr = min(m0x + sg * BWD_BM + lo32, qe - 1);
+      const size_t roff = (size_t)qr * p.hq + h;
+      lse_nxt[sg] = p.lse[roff];
+      dps_nxt[sg] = p.dpsum[roff];
+    }
+  };
   int cur = 0;
   for (int seg = seg0; seg < seg1; ++seg) {
   qs = p.q_ranges[2 * seg];
@@ -364,6 +430,7 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   seg_bounds();
   if (q_lo >= q_hi) continue;
   cur = 0;
+  if constexpr (V_IN_LDS) load_lsedp(q_lo);
   stage_glds(0, q_lo);
   if constexpr (NBUF == 3) stage_glds(1, q_lo + QITER);  // rows clamp to qe-1
 
@@ -372,10 +439,26 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
     // prefetch two stages ahead — always, with clamped rows, so the vmcnt
     // distance stays constant. NBUF=2: full drain (prefetch had one phase).
     pipe_barrier<NBUF == 3 ? GOPS : 0>();
+    // MODE 0: this tile's lse/dpsum were loaded one tile ago and the barrier
+    // above drained them. The empty asm pins the compiler's own wait for the
+    // loads HERE, where nothing is outstanding, so none lands in the subtile
+    // loop behind the prefetch issued below.
+    float lse_cur[V_IN_LDS ? NSUB : 1] = {}, dps_cur[V_IN_LDS ? NSUB : 1] = {};
+    if constexpr (V_IN_LDS) {
+#pragma unroll
+      for (int sg = 0; sg < NSUB; ++sg) {
+        lse_cur[sg] = lse_nxt[sg];
+        dps_cur[sg] = dps_nxt[sg];
+        asm volatile("" : "+v"(lse_cur[sg]), "+v"(dps_cur[sg]));
+      }
+    }
     if constexpr (NBUF == 3) {
       stage_glds(cur == 0 ? 2 : cur - 1, m0 + 2 * QITER);
     } else {
-      if (m0 + QITER < q_hi) stage_glds(cur ^ 1, m0 + QITER);
+      if (m0 + QITER < q_hi) {
+        if constexpr (V_IN_LDS) load_lsedp(m0 + QITER);
+        stage_glds(cur ^ 1, m0 + QITER);
+      }
     }
 #pragma unroll
     for (int sub = 0; sub < NSUB; ++sub) {
@@ -385,24 +468,22 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
     const __bf16* ldb = lds_do(cur) + sub * BWD_BM * ROWE;
     const float* lse_t = nullptr;
     const float* dps_t = nullptr;
-    float lsedp_reg = 0.f;  // MODE0: lanes 0-31 lse, 32-63 dpsum (bpermute)
+    // MODE0: row (lane & 31) of this subtile (bpermute)
+    const float lse_reg = lse_cur[V_IN_LDS ? sub : 0];
+    const float dps_reg = dps_cur[V_IN_LDS ? sub : 0];
     if constexpr (!V_IN_LDS) {
       lse_t = lds_lse(cur) + sub * 2 * BWD_BM;
       dps_t = lse_t + BWD_BM;
-    } else {
-      const int qr = min(ms + lo32, qe - 1);
-      lsedp_reg = (lane < 32) ? p.lse[(size_t)qr * p.hq + h]
-                              : p.dpsum[(size_t)qr * p.hq + h];
     }
     auto lse_at = [&](int rl) -> float {
       if constexpr (!V_IN_LDS) return lse_t[rl];
       return __uint_as_float(__builtin_amdgcn_ds_bpermute(
-          rl << 2, __float_as_uint(lsedp_reg)));
+          rl << 2, __float_as_uint(lse_reg)));
     };
     auto dps_at = [&](int rl) -> float {
       if constexpr (!V_IN_LDS) return dps_t[rl];
       return __uint_as_float(__builtin_amdgcn_ds_bpermute(
-          (32 + rl) << 2, __float_as_uint(lsedp_reg)));
+          rl << 2, __float_as_uint(dps_reg)));
     };
 
     if (wave_live && ms + BWD_BM > wq_lo && ms < wq_hi) {
@@ -449,11 +530,16 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
           (ms + BWD_BM <= wq_hi) && (ms >= qs) && (n0 + BWD_BN <= ke) &&
           !((atype == 1 || atype == 3) && (n0 + BWD_BN - 1 > ms + (ke - qe))) &&
           !((atype == 2 || atype == 3) && (n0 < ms + BWD_BM - 1 + (ks - qs)));
+      // each row's lse is fetched once and shared by the all_live check and
+      // the exponent (MODE 0: one ds_bpermute per row instead of two)
+      float lqv[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) lqv[r] = lse_at(crow(r, hi));
       bool all_live = interior;
       if (interior) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float lq = lse_at(crow(r, hi));
+          const float lq = lqv[r];
           all_live = all_live && (lq != INFINITY) && (lq != -INFINITY);
         }
       }
@@ -461,7 +547,7 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int rl = crow(r, hi);
-          const float pij = fast_exp2(s[r] * sl2 - lse_at(rl) * log2e);
+          const float pij = fast_exp2(s[r] * sl2 - lqv[r] * log2e);
           if constexpr (WANT_DV) pv[r] = pij;
           if constexpr (WANT_DK)
             dsv[r] = pij * (dp[r] - dps_at(rl)) * p.scale;
@@ -470,7 +556,7 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int qrow = ms + crow(r, hi);
-          const float lq = (qrow < qe) ? lse_at(crow(r, hi)) : INFINITY;
+          const float lq = (qrow < qe) ? lqv[r] : INFINITY;
           bool ok = (qrow < wq_hi) && (qrow >= qs) && lq != INFINITY &&
                     lq != -INFINITY && kk < ke;
           if (atype == 1 || atype == 3) ok = ok && (kk - qrow <= ke - qe);
@@ -649,12 +735,19 @@ void ffa_bwd_dq_kernel(BwdParams p) {
   const int wz = (int)(w2 / p.work_ny);
   const int ri = wz;
   const int h = p.head_major ? wx : wy;
-  const int wb = p.head_major ? wy : wx;
+  const int wb_lin = p.head_major ? wy : wx;
   const int qs = p.q_ranges[2 * ri], qe = p.q_ranges[2 * ri + 1];
-  const int mblk0 = qs + wb * (BWD_BM * WAVES);
-  if (mblk0 >= qe) continue;
+  const int nqb = (qe - qs + BWD_BM * WAVES - 1) / (BWD_BM * WAVES);
+  if (wb_lin >= nqb) continue;
   const int seg0 = p.seg_starts ? p.seg_starts[ri] : ri;
   const int seg1 = p.seg_starts ? p.seg_starts[ri + 1] : ri + 1;
+  // causal / bi-causal: a q block's k loop grows with its row index, so hand
+  // the range's blocks out last-first — longest work first leaves the short
+  // blocks to fill the final, uneven round (the dkv pass gets this order by
+  // construction). Keyed on the range's first k segment.
+  const int at0 = p.attn_type_map ? p.attn_type_map[seg0] : 0;
+  const int wb = (at0 == 1 || at0 == 3) ? nqb - 1 - wb_lin : wb_lin;
+  const int mblk0 = qs + wb * (BWD_BM * WAVES);
   int ks, ke, atype;
 
   const int tid = threadIdx.x;
