@@ -15,7 +15,12 @@
 //       S^T = K Q^T ; dP^T = V dO^T ; dS^T (base-2 recompute, like the fwd)
 //       dQ += dS K   (dS^T -> A-frag in-register via permlane, K B-frags by
 //                     tr16 reads off the staged row image)
-//     dQ is atomic-added once at the end.
+//     dQ is atomic-added once at the end. The stage loads are issued outside
+//     the compiler's waitcnt tracking (glds16_untracked, as in the fused
+//     dK/dV mode below): the barrier's counted vmcnt is the only
+//     vector-memory wait in the k loop, the kernel drains by hand at the end
+//     of every k segment, and the LDS fragment reads of all three matmuls run
+//     one step ahead of their MFMA.
 //   ffa_bwd_dkv_kernel     k-outer: a workgroup owns WAVES x 32 k rows; each
 //     wave accumulates its dK and/or dV tile in registers over the q loop and
 //     atomic-adds it once at the end. Q/dO tiles are staged per iteration:
@@ -47,22 +52,6 @@
 #define BWD_BM 32    // q rows per tile
 
 DEV_INLINE bool wave_alive(int m0, int qe) { return m0 < qe; }
-
-// 16-byte-per-lane LDS-DMA (global_load_lds_dwordx4) issued from inline asm,
-// so the compiler's waitcnt pass does not track it. The builtin form leaves a
-// "pending LDS write" on the VM counter in that pass, and it then puts
-// `s_waitcnt vmcnt(0)` in front of the first ds_read_b64_tr_b16 that follows
-// (the tr16 builtin is not marked read-only, so it is ordered against the
-// DMA) — in a prefetch pipeline that drains the next tile's DMA in the
-// middle of the compute phase meant to cover it. Callers own the ordering:
-// the staged image may only be read after a pipe_barrier that retires it.
-// lds_byte is the wave-uniform LDS byte address of the destination; lane l
-// lands at lds_byte + 16 * l.
-DEV_INLINE void glds16_untracked(const void* gsrc, int lds_byte) {
-  const int m0v = __builtin_amdgcn_readfirstlane(lds_byte);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-               :: "s"(m0v), "v"(gsrc) : "memory", "m0");
-}
 
 struct BwdParams {
   const bf16_t* dout;
@@ -800,8 +789,8 @@ void ffa_bwd_dq_kernel(BwdParams p) {
       dof[dd] = *(const bf16x8*)(dp + dd * 16 + hi * 8);
     }
   }
-  const float lse_q = qvalid ? p.lse[(size_t)qrow * p.hq + h] : INFINITY;
-  const float dpsum_q = qvalid ? p.dpsum[(size_t)qrow * p.hq + h] : 0.f;
+  float lse_q = qvalid ? p.lse[(size_t)qrow * p.hq + h] : INFINITY;
+  float dpsum_q = qvalid ? p.dpsum[(size_t)qrow * p.hq + h] : 0.f;
   const bool row_live = qvalid && lse_q != INFINITY && lse_q != -INFINITY;
 
   // block + wave k-loop bounds (recomputed per k segment)
@@ -824,6 +813,11 @@ void ffa_bwd_dq_kernel(BwdParams p) {
   constexpr int ROWS_PER_GLDS = 1024 / ROWB;
   static_assert(KITER / WAVES >= ROWS_PER_GLDS, "stage rows per wave");
   constexpr int GLDS_PER_WAVE = (KITER / WAVES) / ROWS_PER_GLDS;
+  const int smem_byte = (int)(unsigned long long)(
+      (__attribute__((address_space(3))) const char*)smem);
+  // Issued outside the compiler's waitcnt tracking (glds16_untracked): the
+  // counted wait of pipe_barrier is the ONLY thing that orders the ring, and
+  // drain_vm() at the end of each k segment owns the drain.
   auto stage_glds = [&](int buf, int n0x) {
 #pragma unroll
     for (int gi = 0; gi < GLDS_PER_WAVE; ++gi) {
@@ -834,16 +828,10 @@ void ffa_bwd_dq_kernel(BwdParams p) {
       int cs = c ^ ((r & SW32M) << 1);
       if (cs >= VSLOTS) cs = 0;
       const int csw = cs * 8;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(
-              p.k + (size_t)kr * k_pitch + (size_t)kh * D + csw),
-          (__attribute__((address_space(3))) unsigned int*)&lds_k(buf)[r0 * ROWE],
-          16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(
-              p.v + (size_t)kr * k_pitch + (size_t)kh * D + csw),
-          (__attribute__((address_space(3))) unsigned int*)&lds_v(buf)[r0 * ROWE],
-          16, 0, 0);
+      const int lk = smem_byte + (2 * buf * KITER + r0) * ROWB;
+      glds16_untracked(p.k + (size_t)kr * k_pitch + (size_t)kh * D + csw, lk);
+      glds16_untracked(p.v + (size_t)kr * k_pitch + (size_t)kh * D + csw,
+                       lk + KITER * ROWB);
     }
   };
 
@@ -859,10 +847,26 @@ void ffa_bwd_dq_kernel(BwdParams p) {
   cur = 0;
   stage_glds(0, k_lo);
   if constexpr (NBUF == 3) stage_glds(1, k_lo + KITER);  // rows clamp to ke-1
+  // Q/dO fragments, lse and dpsum are the only compiler-tracked vector-memory
+  // loads of a work item. Pin the compiler's wait for them HERE, outside the
+  // k loop: placed at their first use it would sit inside the loop as a
+  // vmcnt(0) per iteration. (It also drains the two prologue stages, which
+  // the first barrier is about to wait for anyway.)
+#pragma unroll
+  for (int dd = 0; dd < DF; ++dd) {
+    pin_vgpr(qf[dd]);
+    pin_vgpr(dof[dd]);
+  }
+  pin_vgpr(lse_q);
+  pin_vgpr(dpsum_q);
 
   for (int n0 = k_lo; n0 < k_hi; n0 += KITER) {
-    // NBUF=3: constant-distance barrier — wait only for buf[cur], keep the
-    // next stage in flight, prefetch two ahead (clamped). NBUF=2: full drain.
+    // vmcnt accounting (per wave; the counter retires in issue order): after
+    // stage(cur) this wave has issued exactly one more stage, GOPS ops, and
+    // nothing else — the k loop holds no other vector-memory op, and the dq
+    // atomics of the previous strided work item are older than both stages.
+    // NBUF=3: vmcnt(GOPS) therefore retires buf[cur] and keeps the next
+    // stage in flight; prefetch two ahead (clamped). NBUF=2: full drain.
     pipe_barrier<NBUF == 3 ? GOPS : 0>();
     if constexpr (NBUF == 3) {
       stage_glds(cur == 0 ? 2 : cur - 1, n0 + 2 * KITER);
@@ -878,14 +882,31 @@ void ffa_bwd_dq_kernel(BwdParams p) {
 
     if (wave_alive(m0, qe) && ns + BWD_BN > wk_lo && ns < wk_hi) {
       // ---- S^T = K Q^T ; dP^T = V dO^T (K/V A-frags from LDS rows) ----
+      // software-pipelined: the K/V fragment pair of step dd+1 is issued
+      // under the two MFMAs of step dd; the sched_group_barriers hold that
+      // order against the scheduler
       f32x16 sA = (f32x16)(0.f), dpA = (f32x16)(0.f);
+      {
+        const int off0 = swz(lo32, lo32 * ROWB + hi * 16);
+        bf16x8 kf = *(const bf16x8*)((const char*)lkb + off0);
+        bf16x8 vf = *(const bf16x8*)((const char*)lvb + off0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read x2
 #pragma unroll
-      for (int dd = 0; dd < DF; ++dd) {
-        const int off = swz(lo32, lo32 * ROWB + dd * 32 + hi * 16);
-        bf16x8 kf = *(const bf16x8*)((const char*)lkb + off);
-        bf16x8 vf = *(const bf16x8*)((const char*)lvb + off);
-        sA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[dd], sA, 0, 0, 0);
-        dpA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[dd], dpA, 0, 0, 0);
+        for (int dd = 0; dd < DF; ++dd) {
+          bf16x8 kn = kf, vn = vf;
+          if (dd + 1 < DF) {
+            const int off = swz(lo32, lo32 * ROWB + (dd + 1) * 32 + hi * 16);
+            kn = *(const bf16x8*)((const char*)lkb + off);
+            vn = *(const bf16x8*)((const char*)lvb + off);
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+          }
+          sA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[dd], sA, 0, 0, 0);
+          dpA =
+              __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[dd], dpA, 0, 0, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA x2
+          kf = kn;
+          vf = vn;
+        }
       }
 
       float dsv[16];
@@ -945,9 +966,12 @@ void ffa_bwd_dq_kernel(BwdParams p) {
         const int rb3 = (row1 + 16) * ROWB + lane8;
         // software-pipelined: step j+1's fragment reads issue under step j's
         // MFMA so the ~50-cycle LDS latency hides under the matrix op (the
-        // serialized read->wait->mfma form parks the wave per fragment)
+        // serialized read->wait->mfma form parks the wave per fragment).
+        // The sched_group_barriers hold the order: without them the
+        // scheduler sinks each tr16 pair back in front of its own MFMA.
         bf16x8 bcur = tr16_frag(k_base + rb0 + ((16 * qhalf2 * 2) ^ sw0),
                                 k_base + rb1 + ((16 * qhalf2 * 2) ^ sw1));
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read x2
 #pragma unroll
         for (int j = 0; j < 2 * DT; ++j) {
           bf16x8 bnext = bcur;
@@ -959,9 +983,11 @@ void ffa_bwd_dq_kernel(BwdParams p) {
             else
               bnext = tr16_frag(k_base + rb0 + (dcoln ^ sw0),
                                 k_base + rb1 + (dcoln ^ sw1));
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
           }
           acc_dq[j >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
               (j & 1) ? dsa1 : dsa0, bcur, acc_dq[j >> 1], 0, 0, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA x1
           bcur = bnext;
         }
       }
@@ -969,7 +995,12 @@ void ffa_bwd_dq_kernel(BwdParams p) {
     }  // sub
     cur = (NBUF == 3) ? (cur == 2 ? 0 : cur + 1) : (cur ^ 1);
   }
-  __syncthreads();  // this segment's LDS reads retired before restaging
+  // End of a k segment: up to two clamped-row prefetches are still in flight
+  // (NBUF=3) and nothing else waits for them — drain by hand, then barrier so
+  // every wave's LDS reads are retired before the next segment, the next
+  // strided work item or nobody (kernel end) restages the ring.
+  drain_vm();
+  __syncthreads();
   }  // seg
 
   // ---- store dq once (atomicAdd: q_ranges of different slices may overlap) ----

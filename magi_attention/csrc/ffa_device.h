@@ -1,5 +1,6 @@
 // ffa_device.h — device helpers shared by the FFA kernels (gfx950, wave64):
-// vector typedefs, the software-pipelined LDS-DMA barrier, and the MFMA
+// vector typedefs, the software-pipelined LDS-DMA barrier, the LDS-DMA issue
+// that bypasses the compiler's waitcnt tracking with its drain, and the MFMA
 // 32x32x16 fragment helpers. Included by ffa_fwd.hip, ffa_bwd.hip,
 // ffa_index.hip, ffa_index_bwd.hip, ffa_fwd_fp8.hip and ffa_index_fp8.hip;
 // everything here is force-inlined.
@@ -26,6 +27,38 @@ template <int VM>
 DEV_INLINE void pipe_barrier() {
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier"
                :: "n"(VM) : "memory");
+}
+
+// 16-byte-per-lane LDS-DMA (global_load_lds_dwordx4) issued from inline asm,
+// so the compiler's waitcnt pass does not track it. The builtin form leaves a
+// "pending LDS write" on the VM counter in that pass, and it then puts
+// `s_waitcnt vmcnt(0)` in front of the first ds_read_b64_tr_b16 that follows
+// (the tr16 builtin is not marked read-only, so it is ordered against the
+// DMA) — in a prefetch pipeline that drains the next tile's DMA in the
+// middle of the compute phase meant to cover it. Callers own the ordering:
+// the staged image may only be read after a pipe_barrier that retires it,
+// and a kernel that restages or leaves LDS must drain with drain_vm() first —
+// no compiler-placed wait covers these loads.
+// lds_byte is the wave-uniform LDS byte address of the destination; lane l
+// lands at lds_byte + 16 * l.
+DEV_INLINE void glds16_untracked(const void* gsrc, int lds_byte) {
+  const int m0v = __builtin_amdgcn_readfirstlane(lds_byte);
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
+               :: "s"(m0v), "v"(gsrc) : "memory", "m0");
+}
+
+// Explicit full drain of the vector-memory counter: the wait the compiler
+// would have placed for tracked loads, owned by hand for the untracked ones.
+DEV_INLINE void drain_vm() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// Forces the compiler's own wait for whatever load produced x to this point
+// (and keeps x in a VGPR): used to keep such waits out of a loop whose
+// vmcnt distance is owned by hand.
+template <class T>
+DEV_INLINE void pin_vgpr(T& x) {
+  asm volatile("" : "+v"(x));
 }
 
 DEV_INLINE float warp_xor32(float v) { return __shfl_xor(v, 32, 64); }

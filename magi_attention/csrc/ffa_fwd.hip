@@ -6,6 +6,13 @@
 //     -> softmax row-reduce is 15 in-register fmax + one shfl_xor(32)
 //   - P -> bf16 A-fragments rebuilt in-register via cvt_pk + permlane32_swap
 //     (no LDS round trip for P)
+//   - K/V staged 64 rows per barrier into a swizzled LDS ring by LDS-DMA
+//     issued outside the compiler's waitcnt tracking: the barrier's counted
+//     vmcnt is the only vector-memory wait in the k loop, and the kernel
+//     drains by hand at the end of every k segment. LDS fragment reads run
+//     one step ahead of the MFMA that consumes them.
+//   - a causal / bi-causal range's q blocks are handed out last-first
+//     (longest k loop first)
 //   - fp32 out accumulator merged in gmem under 2-slot range locks
 //     (replaces the reference's atomicCAS range-lock epilogue,
 //      epilogue_fwd.hpp:271-424), so overlapping q_ranges and cross-launch
@@ -84,14 +91,23 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
   const int wz = (int)(w2 / p.work_ny);
   const int ri = p.head_major ? wz : wy;
   const int h = p.head_major ? wx : wz;
-  const int mb = p.head_major ? wy : wx;
+  const int mb_lin = p.head_major ? wy : wx;
   const int qs = p.q_ranges[2 * ri], qe = p.q_ranges[2 * ri + 1];
-  const int m0 = qs + mb * (32 * WAVES);
-  if (m0 >= qe) continue;                     // uniform across block
+  const int nqb = (qe - qs + 32 * WAVES - 1) / (32 * WAVES);
+  if (mb_lin >= nqb) continue;                // uniform across block
   // auto_range_merge: iterate this unique q range's k segments in-kernel,
   // online softmax carried across them (reference merge_range.cu semantics)
   const int seg0 = p.qk_starts ? p.qk_starts[ri] : ri;
   const int seg1 = p.qk_starts ? p.qk_starts[ri + 1] : ri + 1;
+  // causal / bi-causal: a q block's k loop grows with its row index, so hand
+  // the range's blocks out last-first (longest work first, as the dQ pass
+  // does); keyed on the range's first k segment. The mapping is a function
+  // of the flattened work index alone, so the exact grid and the cu_margin
+  // strided walk agree on it.
+  const int at0 =
+      (p.attn_type_map && seg0 < seg1) ? p.attn_type_map[seg0] : 0;
+  const int mb = (at0 == 1 || at0 == 3) ? nqb - 1 - mb_lin : mb_lin;
+  const int m0 = qs + mb * (32 * WAVES);
   int ks, ke, atype;
 
   const int lane = threadIdx.x & 63;
@@ -152,8 +168,11 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
   // covers the prefetch latency the 32-row register pipeline could not.
   // NBUF=3 (r2, ported from the bwd 3-ring): constant-distance vmcnt wait —
   // the barrier waits only for the one stage it needs and the prefetch gets
-  // two compute phases to land, removing the full vmcnt(0) drain per
-  // iteration (the dominant stall on short ranges / 8k).
+  // two compute phases to land. That holds only because the stage loads are
+  // issued outside the compiler's waitcnt tracking (see stage_glds): with the
+  // builtin LDS-DMA the compiler drained the ring with a vmcnt(0) in front
+  // of the first tr16 V read of every subtile, one phase deep in effect.
+  // The barrier's counted wait is the only vector-memory wait in the k loop.
   constexpr int KITER = 2 * FFA_BN;
   __shared__ __attribute__((aligned(16))) char fsmem[NBUF * 2 * KITER * ROWB];
   auto lds_k = [&](int buf) -> __bf16* {
@@ -187,6 +206,11 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
   static_assert(KITER / WAVES >= ROWS_PER_GLDS, "stage rows per wave");
   constexpr int GLDS_PER_WAVE = (KITER / WAVES) / ROWS_PER_GLDS;
   constexpr int GOPS = 2 * GLDS_PER_WAVE;  // vm ops per stage call per wave
+  const int fsmem_byte = (int)(unsigned long long)(
+      (__attribute__((address_space(3))) const char*)fsmem);
+  // Issued outside the compiler's waitcnt tracking (glds16_untracked): the
+  // counted wait of pipe_barrier is the ONLY thing that orders the ring, and
+  // drain_vm() below owns every point where LDS is restaged or left.
   auto stage_glds = [&](int buf, int n0x) {
 #pragma unroll
     for (int gi = 0; gi < GLDS_PER_WAVE; ++gi) {
@@ -197,16 +221,9 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
       int cs = c ^ ((r & SW32M) << 1);
       if (cs >= VSLOTS) cs = 0;  // padding slot: any in-bounds source
       const int csw = cs * 8;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(
-              kbase + (size_t)kr * k_pitch + csw),
-          (__attribute__((address_space(3))) unsigned int*)&lds_k(buf)[r0 * ROWE],
-          16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)(
-              vbase + (size_t)kr * k_pitch + csw),
-          (__attribute__((address_space(3))) unsigned int*)&lds_v(buf)[r0 * ROWE],
-          16, 0, 0);
+      const int lk = fsmem_byte + (2 * buf * KITER + r0) * ROWB;
+      glds16_untracked(kbase + (size_t)kr * k_pitch + csw, lk);
+      glds16_untracked(vbase + (size_t)kr * k_pitch + csw, lk + KITER * ROWB);
     }
   };
 
@@ -342,21 +359,35 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
       const int v_base = (int)(unsigned long long)(
           (__attribute__((address_space(3))) const char*)lvb);
       const int lane8 = (lane & 3) * 8;
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt) {
+      // step j = (tt, dt), tt outer as before. Software-pipelined: the tr16
+      // pair of step j+1 is issued under the MFMA of step j (across tt too),
+      // so each MFMA waits with a counted lgkmcnt for its own fragment only.
+      // The sched_group_barriers hold that order; without them the
+      // scheduler sinks every pair back in front of its MFMA.
+      auto vfrag = [&](int j) {
+        const int tt = j / DT, dt = j % DT;
         const int row0 = 16 * tt + 8 * hi + jrow;
         const int row1 = row0 + 4;
         const int sw0 = (row0 & SW32M) << 5;
         const int sw1 = (row1 & SW32M) << 5;
         const int rb0 = v_base + row0 * ROWB + lane8;
         const int rb1 = v_base + row1 * ROWB + lane8;
+        const int dcol = (dt * 32 + 16 * qhalf) * 2;
+        return tr16_frag(rb0 + (dcol ^ sw0), rb1 + (dcol ^ sw1));
+      };
+      bf16x8 bcur = vfrag(0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read x2
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          const int dcol = (dt * 32 + 16 * qhalf) * 2;
-          bf16x8 bv = tr16_frag(rb0 + (dcol ^ sw0), rb1 + (dcol ^ sw1));
-          acc_o[dt] =
-              __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[tt], bv, acc_o[dt], 0, 0, 0);
+      for (int j = 0; j < 2 * DT; ++j) {
+        bf16x8 bnext = bcur;
+        if (j + 1 < 2 * DT) {
+          bnext = vfrag(j + 1);
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         }
+        acc_o[j % DT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            pa[j / DT], bcur, acc_o[j % DT], 0, 0, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA x1
+        bcur = bnext;
       }
     }
   };
@@ -373,10 +404,22 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
     cur = 0;
     stage_glds(0, b_lo);
     if constexpr (NBUF == 3) stage_glds(1, b_lo + KITER);  // rows clamp
+    // The Q fragment loads are the only compiler-tracked vector-memory loads
+    // of a work item. Pin the compiler's wait for them HERE, outside the k
+    // loop: placed at their first use it would sit inside the loop as a
+    // vmcnt(0) per iteration. (It also drains the two prologue stages, which
+    // the first barrier is about to wait for anyway.)
+#pragma unroll
+    for (int dd = 0; dd < DF; ++dd) pin_vgpr(qf[dd]);
     for (int n0 = b_lo; n0 < b_hi; n0 += KITER) {
-      // NBUF=3: wait ONLY for buf[cur] (leave the next stage in flight),
-      // then prefetch two stages ahead — always, with clamped rows, so the
-      // vmcnt distance stays constant. NBUF=2: full drain.
+      // vmcnt accounting (per wave; the counter retires in issue order):
+      // after stage(cur) this wave has issued exactly one more stage, GOPS
+      // ops, and nothing else — the k loop holds no other vector-memory op.
+      // Anything older (Q loads, the previous work item's epilogue stores)
+      // only retires earlier. NBUF=3: vmcnt(GOPS) therefore retires
+      // buf[cur] and leaves the next stage in flight; then prefetch two
+      // stages ahead — always, with clamped rows, so the distance stays
+      // constant. NBUF=2: full drain.
       pipe_barrier<NBUF == 3 ? GOPS : 0>();
       if constexpr (NBUF == 3) {
         stage_glds(cur == 0 ? 2 : cur - 1, n0 + 2 * KITER);
@@ -392,8 +435,12 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
       }
       cur = (NBUF == 3) ? (cur == 2 ? 0 : cur + 1) : (cur ^ 1);
     }
-    // LDS reads of this segment retired before the next segment's staging
-    // (implicit vmcnt(0) drains the in-flight prefetches too)
+    // End of a k segment: up to two clamped-row prefetches are still in
+    // flight (NBUF=3) and nothing else will wait for them — drain them by
+    // hand, then barrier so every wave's LDS reads of this segment are
+    // retired before the next segment, the next strided work item or nobody
+    // (kernel end) restages the ring. The epilogue runs behind this drain.
+    drain_vm();
     __syncthreads();
   }
   if (any_seg) {
