@@ -218,7 +218,24 @@ int magi_grpcoll_pull(const struct magi_grpcoll_pull_args* args);
  * indices_2d[i] lists the GLOBAL K rows attended by q token row i, shared
  * by all hq query heads of that row; -1 = contiguous tail padding. KV heads
  * are folded into the K row dimension (hk must be 1). The reference is
- * forward-only here; magi_ffa_bwd_index below adds the backward. */
+ * forward-only here; magi_ffa_bwd_index below adds the backward.
+ *
+ * Optional trailing fields (null / zero = off, and then out and lse are
+ * bit-identical to a call without them):
+ *   sink       f32 attention-sink logits folded into the kernel's epilogue in
+ *              fp32, before the single rounding of out: with lse_sink =
+ *              logsumexp_j sink[.., j, head], a live row stores lse' =
+ *              logaddexp(lse, lse_sink) and out * exp(lse - lse'); a row whose
+ *              list is all -1 stores lse = lse_sink and leaves out at the
+ *              caller's zero. Layouts as magi_sink_args: sink_ssh=0 ->
+ *              sink[s_sink, hq]; sink_ssh=1 -> sink[total_q, s_sink, hq].
+ *   max_logits f32 [hq], caller-initialised to -inf: per-head atomic max over
+ *              all tokens of the scaled (softcapped, if on) logits of valid
+ *              slots. All-padding rows and sink logits do not enter it.
+ * Validation, in this order, all before any HIP call: -1 null pointer, -2 d
+ * not in {64, 128}, -3 hk != 1, -4 max_topk not a positive multiple of 64,
+ * -5 sink != NULL with s_sink outside [1, 8]; then total_q <= 0 returns 0
+ * without a launch. */
 typedef struct magi_ffa_index_args {
   const void* q;              /* bf16 [total_q, hq, d] */
   const void* k;              /* bf16 [total_k, 1, d] */
@@ -236,6 +253,10 @@ typedef struct magi_ffa_index_args {
   float softcap;
   int32_t out_is_fp32;
   void* stream;               /* hipStream_t */
+  const float* sink;          /* f32 sink logits, NULL = no sink */
+  int32_t s_sink;             /* 1..8 when sink != NULL */
+  int32_t sink_ssh;           /* 0 = "sh" [s_sink, hq], 1 = "ssh" [total_q, s_sink, hq] */
+  float* max_logits;          /* f32 [hq] init -inf, NULL = off */
 } magi_ffa_index_args;
 
 int magi_ffa_fwd_index(const magi_ffa_index_args* args);
@@ -248,8 +269,10 @@ int magi_ffa_fwd_index(const magi_ffa_index_args* args);
  * to e4m3, fp32 accumulate); softcap is supported. Validation order and
  * codes are those of magi_ffa_fwd_index, all returned before any HIP call:
  * -1 null pointer, -2 d not in {64, 128}, -3 hk != 1, -4 max_topk not a
- * positive multiple of 64; total_q <= 0 or hq <= 0 returns 0 without a
- * launch. */
+ * positive multiple of 64, -5 sink != NULL with s_sink outside [1, 8];
+ * total_q <= 0 or hq <= 0 returns 0 without a launch. sink and max_logits
+ * behave as for magi_ffa_fwd_index; the sink is folded after the lse has left
+ * the 2^8-offset domain of the fp8 running sum. */
 int magi_ffa_fwd_index_fp8(const magi_ffa_index_args* args);
 
 /* Index-attention backward (beyond the reference, whose autograd returns None

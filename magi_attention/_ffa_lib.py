@@ -153,6 +153,28 @@ class MagiFfaIndexArgs(ctypes.Structure):
         ("stream", ctypes.c_void_p),
     ]
 
+    # The native entries read the whole C struct, optional tail included, so
+    # no instance may be shorter than it: constructing this class hands back
+    # the full-length subclass below, its tail zero-filled (= off). The
+    # sixteen members above keep their names, order and offsets, and
+    # sink=/s_sink=/sink_ssh=/max_logits= are accepted as keywords.
+    def __new__(cls, *args, **kw):
+        if cls is MagiFfaIndexArgs:
+            cls = _MagiFfaIndexArgsFull
+        return super().__new__(cls)
+
+
+class _MagiFfaIndexArgsFull(MagiFfaIndexArgs):
+    """MagiFfaIndexArgs plus the optional tail of magi_ffa_index_args
+    (ctypes appends a subclass's fields after its base's)"""
+
+    _fields_ = [
+        ("sink", ctypes.c_void_p),        # f32 sink logits, null = no sink
+        ("s_sink", ctypes.c_int32),       # 1..8 when sink is set
+        ("sink_ssh", ctypes.c_int32),     # 0 = "sh", 1 = "ssh"
+        ("max_logits", ctypes.c_void_p),  # f32 [hq] preset to -inf, null = off
+    ]
+
 
 class MagiFfaIndexBwdArgs(ctypes.Structure):
     """mirrors magi_ffa_index_bwd_args (index-attention backward)"""

@@ -63,6 +63,59 @@ DEV_INLINE void pin_vgpr(T& x) {
 
 DEV_INLINE float warp_xor32(float v) { return __shfl_xor(v, 32, 64); }
 
+// ---- index-attention epilogue helpers (ffa_index.hip, ffa_index_fp8.hip) ----
+
+// lse over the s_sink (1..8, checked by the host entry) attention-sink logits
+// of (token, head), fp32 with the max subtracted — the arithmetic of
+// sink_postprocess_kernel in range_ops.hip. Layouts of magi_sink_args:
+// ssh = 0 -> sink[j * hq + head], ssh = 1 -> sink[(tok * s_sink + j) * hq +
+// head]. The 8 predicated loads are unrolled so the logits stay in registers
+// (a runtime-indexed array would go to scratch); an absent slot is -inf and
+// adds an exact 0. All logits -inf gives -inf.
+DEV_INLINE float index_sink_lse(const float* sink, int s_sink, int ssh,
+                                long long tok, int hq, int head) {
+  const float* sp = sink + (ssh ? tok * s_sink * (long long)hq : 0ll) + head;
+  float sv[8];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    sv[j] = (j < s_sink) ? sp[(long long)j * hq] : -INFINITY;
+    mx = fmaxf(mx, sv[j]);
+  }
+  if (mx == -INFINITY) return -INFINITY;
+  float l = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) l += expf(sv[j] - mx);
+  return mx + logf(l);
+}
+
+// Folds lse_sink into a row's (lse, output scale): live row -> lse' =
+// logaddexp(lse, lse_sink) and the output scale times exp(lse - lse'); empty
+// row (lse = -inf) -> lse = lse_sink, scale untouched (its output is never
+// stored). lse_sink = -inf changes nothing, bit for bit.
+DEV_INLINE void index_sink_fold(float lse_sink, float& lse, float& out_scale) {
+  if (lse_sink == -INFINITY) return;
+  if (lse == -INFINITY) {
+    lse = lse_sink;
+    return;
+  }
+  const float m = fmaxf(lse, lse_sink);
+  const float lse2 = m + logf(expf(lse - m) + expf(lse_sink - m));
+  out_scale *= expf(lse - lse2);
+  lse = lse2;
+}
+
+// Per-head running maximum. In the index kernels a lane owns one query head,
+// so there is nothing to reduce across the wave beyond the two 32-lane halves
+// (the caller's row max already is). The maximum only grows, so a plain read
+// that is stale can only be too small: it filters out almost every atomic
+// (all tokens hit the same hq addresses) and never drops a needed one.
+DEV_INLINE void head_atomic_max(float* dst, float v) {
+  if (v != -INFINITY &&
+      v > __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    unsafeAtomicMax(dst, v);
+}
+
 // one packed convert (RNE, same as the scalar bf16 cast) — the C version
 // lowers to 2 cvt + shift + or, 4x the issue slots (guide: cvt_pk idiom)
 DEV_INLINE unsigned pack_bf16_pair(float lo, float hi) {

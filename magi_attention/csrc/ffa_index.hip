@@ -23,6 +23,17 @@
 //
 // Compute core (swapped QK^T, softmax layout, defer-max, cvt_pk P rebuild,
 // tr16 V fragments) is the same design as ffa_fwd.hip — see the notes there.
+//
+// Epilogue extras, both off (null pointers, block-uniform branches, k loop
+// untouched, out/lse bit-identical) unless asked for:
+//   - attention sink: a lane owns one query head, so it loads that head's
+//     <= 8 sink logits, takes lse_sink in fp32 and folds it into (lse,
+//     1/l) before the single rounding of out — no second pass over the bf16
+//     out as on the dense route. A row whose list is all -1 stores
+//     lse = lse_sink and leaves out at the host's zero.
+//   - max_logits: per-head atomic max of m_run * ln2 over all tokens; the
+//     defer-max threshold drops to 0 so m_run is the true row max. Sink
+//     logits and all-padding rows do not enter.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -45,6 +56,10 @@ struct IdxParams {
   float scale;
   float softcap;
   long long total_q, total_k;
+  const float* sink;  // null = no sink
+  int s_sink;
+  int sink_ssh;
+  float* max_logits;  // [hq], null = off
 };
 
 template <int D, bool HAS_SOFTCAP, bool OUT_BF16, int WAVES>
@@ -77,7 +92,19 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     }
     count = lo;
   }
-  if (count == 0) return;  // out zero-init + lse -inf preset by the host
+  if (__builtin_expect(count == 0, 0)) {
+    // out zero-init + lse -inf preset by the host; with a sink the row's
+    // softmax mass is the sink's alone: lse = lse_sink, out stays 0
+    if (p.sink) {
+      const int eh = h0 + wave * 32 + lo32;
+      if (eh < p.hq && hi == 0) {
+        const float ls =
+            index_sink_lse(p.sink, p.s_sink, p.sink_ssh, tok, p.hq, eh);
+        if (ls != -INFINITY) p.lse[tok * p.hq + eh] = ls;
+      }
+    }
+    return;
+  }
 
   const int q0 = h0 + wave * 32;       // first query head of this wave
   const int qh = q0 + lo32;            // this lane's query head
@@ -88,6 +115,10 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
   const float sl2 = HAS_SOFTCAP ? p.softcap * 1.4426950408889634f
                                 : p.scale * 1.4426950408889634f;
   const float cap_pre = HAS_SOFTCAP ? p.scale / p.softcap : 0.f;
+  // max_logits reads m_run as the TRUE row max in the epilogue — no defer
+  // slack then (as ffa_fwd.hip); block-uniform, 8 when off
+  const float defer_thr = __uint_as_float(__builtin_amdgcn_readfirstlane(
+      __float_as_uint(p.max_logits ? 0.f : 8.f)));  // pinned to an SGPR
 
   constexpr int ROWB = D * 2;          // bf16 row bytes (D=64 -> 128, D=128 -> 256)
   constexpr int ROWE = ROWB / 2;
@@ -192,8 +223,8 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
 
     // ---- defer-max (see ffa_fwd.hip) ----
     const float m_new = fmaxf(m_run, mx);
-    const bool need_rescale =
-        (m_new > m_run + 8.f) || (m_run == -INFINITY && m_new != -INFINITY);
+    const bool need_rescale = (m_new > m_run + defer_thr) ||
+                              (m_run == -INFINITY && m_new != -INFINITY);
     float m_use;
     float alpha;
     if (!__any(need_rescale)) {
@@ -296,11 +327,24 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
   }
 
   // ======================= epilogue (direct store) =======================
-  const float lse_new =
+  float lse_new =
       (l_run > 0.f) ? (m_run + __log2f(l_run)) * 0.6931471805599453f : -INFINITY;
-  const float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
+  float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
 
-  if (l_run > 0.f && qvalid && hi == 0)
+  // per-head max of the scaled (softcapped) logits of valid slots: m_run is
+  // the lane's head-row max in the exp2 domain -> x ln2 (defer_thr is 0 here,
+  // so it is the true max). Invalid heads are -inf and drop out; the sink
+  // below does not enter.
+  if (p.max_logits && qvalid && hi == 0)
+    head_atomic_max(p.max_logits + qh, m_run * 0.6931471805599453f);
+  // sink fold, fp32, ahead of the single rounding of out: the output scale
+  // rides on inv_l. Block-uniform branch; a null sink leaves both untouched.
+  if (p.sink && qvalid)
+    index_sink_fold(
+        index_sink_lse(p.sink, p.s_sink, p.sink_ssh, tok, p.hq, qh),
+        lse_new, inv_l);
+
+  if (lse_new != -INFINITY && qvalid && hi == 0)
     p.lse[tok * p.hq + qh] = lse_new;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -350,6 +394,7 @@ extern "C" int magi_ffa_fwd_index(const magi_ffa_index_args* a) {
   if (a->d != 64 && a->d != 128) return -2;
   if (a->hk != 1) return -3;  // kv heads are folded into K rows (see header)
   if (a->max_topk <= 0 || (a->max_topk & 63) != 0) return -4;
+  if (a->sink && (a->s_sink < 1 || a->s_sink > 8)) return -5;
   if (a->total_q <= 0) return 0;
 
   IdxParams p;
@@ -366,6 +411,10 @@ extern "C" int magi_ffa_fwd_index(const magi_ffa_index_args* a) {
   p.softcap = a->softcap;
   p.total_q = a->total_q;
   p.total_k = a->total_k;
+  p.sink = a->sink;
+  p.s_sink = a->s_sink;
+  p.sink_ssh = a->sink_ssh;
+  p.max_logits = a->max_logits;
 
   // head-block = 32*W query heads; pick W so one wave-set covers hq (DiT
   // ratio 128 -> 4 waves; small-ratio MHA shapes keep lanes busy at W=1)

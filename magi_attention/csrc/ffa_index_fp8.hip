@@ -34,6 +34,12 @@
 // after them. The row XOR ((d >> 5) & 3) << 3 spreads the byte writes over
 // banks and is uniform across one B-fragment read (32 consecutive d), so the
 // reads stay conflict-free with the 40/72-byte row pitch.
+//
+// Epilogue extras (off = null pointers, out/lse bit-identical): the attention
+// sink is folded in fp32 after the lse has left the 2^8-offset domain, and
+// max_logits takes a per-head atomic max of m_run * ln2 (no defer-max here,
+// so m_run is the true row max) — see ffa_index.hip. A count == 0 row with a
+// sink stores lse = lse_sink before it returns.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -60,6 +66,10 @@ struct Idx8Params {
   float scale;
   float softcap;
   long long total_q, total_k;
+  const float* sink;  // null = no sink
+  int s_sink;
+  int sink_ssh;
+  float* max_logits;  // [hq], null = off
 };
 
 // Register budget: the D=128 instances need ~180 registers (64 accumulator +
@@ -95,7 +105,19 @@ ffa_index_fwd_fp8_kernel(Idx8Params p) {
     }
     count = lo;
   }
-  if (count == 0) return;  // out zero-init + lse -inf preset by the host
+  if (__builtin_expect(count == 0, 0)) {
+    // out zero-init + lse -inf preset by the host; with a sink the row's
+    // softmax mass is the sink's alone: lse = lse_sink, out stays 0
+    if (p.sink) {
+      const int eh = h0 + wave * 32 + lo32;
+      if (eh < p.hq && hi == 0) {
+        const float ls =
+            index_sink_lse(p.sink, p.s_sink, p.sink_ssh, tok, p.hq, eh);
+        if (ls != -INFINITY) p.lse[tok * p.hq + eh] = ls;
+      }
+    }
+    return;
+  }
 
   const int q0 = h0 + wave * 32;  // first query head of this wave
   const int qh = q0 + lo32;       // this lane's query head
@@ -281,13 +303,28 @@ ffa_index_fwd_fp8_kernel(Idx8Params p) {
 
   // ======================= epilogue (direct store) =======================
   // the fp8 sum is scaled by 2^MAX_OFFSET relative to exp2(t - m)
-  const float lse_new =
+  float lse_new =
       (l_run > 0.f)
           ? (m_run - MAX_OFFSET + __log2f(l_run)) * 0.6931471805599453f
           : -INFINITY;
-  const float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
+  float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
 
-  if (l_run > 0.f && qvalid && hi == 0)
+  // per-head max of the scaled (softcapped) logits of valid slots: there is
+  // no defer-max here, so m_run is the lane's true head-row max in the exp2
+  // domain -> x ln2. Invalid heads are -inf and drop out; the sink below does
+  // not enter.
+  if (p.max_logits && qvalid && hi == 0)
+    head_atomic_max(p.max_logits + qh, m_run * 0.6931471805599453f);
+  // sink fold, fp32, ahead of the single rounding of out. lse_new has left
+  // the 2^MAX_OFFSET domain above; inv_l still carries it (as l_run does) and
+  // only takes the extra factor exp(lse - lse'). Block-uniform branch; a null
+  // sink leaves both untouched.
+  if (p.sink && qvalid)
+    index_sink_fold(
+        index_sink_lse(p.sink, p.s_sink, p.sink_ssh, tok, p.hq, qh),
+        lse_new, inv_l);
+
+  if (lse_new != -INFINITY && qvalid && hi == 0)
     p.lse[tok * p.hq + qh] = lse_new;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -339,6 +376,7 @@ extern "C" int magi_ffa_fwd_index_fp8(const magi_ffa_index_args* a) {
   if (a->d != 64 && a->d != 128) return -2;
   if (a->hk != 1) return -3;  // kv heads are folded into K rows (see header)
   if (a->max_topk <= 0 || (a->max_topk & 63) != 0) return -4;
+  if (a->sink && (a->s_sink < 1 || a->s_sink > 8)) return -5;
   if (a->total_q <= 0 || a->hq <= 0) return 0;
 
   Idx8Params p;
@@ -355,6 +393,10 @@ extern "C" int magi_ffa_fwd_index_fp8(const magi_ffa_index_args* a) {
   p.softcap = a->softcap;
   p.total_q = a->total_q;
   p.total_k = a->total_k;
+  p.sink = a->sink;
+  p.s_sink = a->s_sink;
+  p.sink_ssh = a->sink_ssh;
+  p.max_logits = a->max_logits;
 
   // head-block = 32*W query heads, chosen from hq as magi_ffa_fwd_index does
   int w = (a->hq > 64) ? 4 : (a->hq > 32 ? 2 : 1);

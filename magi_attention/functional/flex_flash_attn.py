@@ -363,6 +363,10 @@ def _flex_flash_attn_forward_index(
     indices_2d: torch.Tensor,
     softmax_scale: float,
     softcap: float,
+    *,
+    sink: Optional[torch.Tensor] = None,
+    sink_layout: str = "sh",
+    max_logits: Optional[torch.Tensor] = None,
 ) -> tuple[torch.Tensor, AttnForwardMeta]:
     """Index-attention (token-gather) forward: the reference's
     index_attn_indices direct-to-kernel path (flex_flash_attn.py:1358-1390).
@@ -373,7 +377,14 @@ def _flex_flash_attn_forward_index(
 
     q/k/v are all bf16 (csrc/ffa_index.hip) or all fp8-e4m3
     (csrc/ffa_index_fp8.hip: raw e4m3 bytes, no descale factors, the fp8
-    softmax convention of the dense fp8 forward); out is bf16 either way."""
+    softmax convention of the dense fp8 forward); out is bf16 either way.
+
+    sink ("sh" [s_sink, hq] or "ssh" [total_q, s_sink, hq], s_sink in [1, 8])
+    is folded into out and lse inside the kernel's epilogue, in fp32 before
+    out is rounded - there is no separate postprocess launch on this path.
+    max_logits (f32 [hq], preset to -inf by the caller) receives the per-head
+    maximum scaled (softcapped) logit over valid slots and comes back in the
+    meta; sink logits do not enter it."""
     from .._ffa_lib import MagiFfaIndexArgs
 
     is_fp8 = q.dtype == torch.float8_e4m3fn
@@ -394,6 +405,14 @@ def _flex_flash_attn_forward_index(
         f"indices_2d rows ({indices_2d.shape[0]}) must match q token rows ({tq})"
     )
     max_topk = indices_2d.shape[1]
+    sink_f, s_sink = None, 0
+    if sink is not None:
+        sink_f, s_sink = _check_sink(sink, sink_layout, tq, hq)
+    if max_logits is not None:
+        assert max_logits.dtype == torch.float32 and max_logits.shape == (hq,), (
+            "max_logits must be f32 [hq]"
+        )
+        assert max_logits.is_contiguous()
 
     out = torch.zeros(tq, hq, d, dtype=torch.bfloat16, device=q.device)
     lse = torch.full((tq, hq), float("-inf"), dtype=torch.float32, device=q.device)
@@ -405,13 +424,15 @@ def _flex_flash_attn_forward_index(
         hq=hq, hk=hk, d=d,
         softmax_scale=softmax_scale, softcap=softcap,
         out_is_fp32=0, stream=current_stream_ptr(),
+        sink=ptr(sink_f), s_sink=s_sink,
+        sink_ssh=int(sink_layout == "ssh"), max_logits=ptr(max_logits),
     )
     if is_fp8:
         check(_ffa_lib.lib().magi_ffa_fwd_index_fp8(args),
               "magi_ffa_fwd_index_fp8")
     else:
         check(_ffa_lib.lib().magi_ffa_fwd_index(args), "magi_ffa_fwd_index")
-    return out, AttnForwardMeta(lse=lse, max_logits=None)
+    return out, AttnForwardMeta(lse=lse, max_logits=max_logits)
 
 
 def _index_head_dim_pad(d: int) -> int:
@@ -444,11 +465,19 @@ def _flex_flash_attn_backward_index(
     indices_2d: torch.Tensor,
     softmax_scale: float,
     softcap: float,
-) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    sink: Optional[torch.Tensor] = None,
+    sink_layout: str = "sh",
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """Index-attention backward (csrc/ffa_index_bwd.hip): dpsum preprocess,
-    then one gather/scatter kernel. Returns (dq bf16, dk fp32, dv fp32): dq has
-    a single owner per row and is stored directly; dk/dv are fp32 accumulators
-    the kernel scatters into with atomic adds (not deterministic)."""
+    then one gather/scatter kernel. Returns (dq bf16, dk fp32, dv fp32, dsink):
+    dq has a single owner per row and is stored directly; dk/dv are fp32
+    accumulators the kernel scatters into with atomic adds (not deterministic).
+
+    With a sink, lse is the sink-corrected lse the forward saved and out the
+    sink-scaled out, so the kernel's recomputed P and dpsum = rowsum(dO * O)
+    already account for the sink (the dense path's argument); dsink (f32, the
+    sink's shape) comes from magi_ffa_dsink over (sink, lse, dpsum). Without
+    one dsink is None."""
     from .._ffa_lib import MagiFfaIndexBwdArgs
 
     assert q.dtype == torch.bfloat16, "index_attn requires bf16 inputs"
@@ -484,7 +513,73 @@ def _flex_flash_attn_backward_index(
         stream=current_stream_ptr(),
     )
     check(lib.magi_ffa_bwd_index(args), "magi_ffa_bwd_index")
-    return dq, dk, dv
+    dsink = None
+    if sink is not None:
+        from .._ffa_lib import MagiSinkArgs
+
+        sink_f, s_sink = _check_sink(sink, sink_layout, tq, hq)
+        dsink = torch.zeros_like(sink_f)
+        sargs = MagiSinkArgs(
+            lse=ptr(lse), sink=ptr(sink_f), dsink=ptr(dsink), dpsum=ptr(dpsum),
+            total_rows=tq, n_heads=hq, d=d, s_sink=s_sink,
+            ssh=int(sink_layout == "ssh"), stream=current_stream_ptr(),
+        )
+        check(lib.magi_ffa_dsink(sargs), "magi_ffa_dsink")
+    return dq, dk, dv, dsink
+
+
+def _index_attn_forward(ctx, q, k, v, indices_2d, softmax_scale, softcap,
+                        sink, sink_layout, return_max_logits):
+    """forward shared by IndexAttnFunc and IndexAttnSinkFunc"""
+    is_fp8 = q.dtype == torch.float8_e4m3fn
+    d = q.shape[-1]
+    pad = _index_head_dim_pad(d) if is_fp8 else 0
+    max_logits = None
+    if return_max_logits:
+        max_logits = torch.full((q.shape[1],), float("-inf"),
+                                dtype=torch.float32, device=q.device)
+    out, meta = _flex_flash_attn_forward_index(
+        _pad_head_dim(q, pad), _pad_head_dim(k, pad), _pad_head_dim(v, pad),
+        indices_2d, softmax_scale, softcap,
+        sink=sink, sink_layout=sink_layout, max_logits=max_logits,
+    )
+    ctx.save_for_backward(q, k, v, out, meta.lse, indices_2d, sink)
+    ctx.softmax_scale = softmax_scale
+    ctx.softcap = softcap
+    ctx.pad = pad
+    ctx.sink_layout = sink_layout
+    # one call: a second mark_non_differentiable would replace the first
+    if max_logits is not None:
+        ctx.mark_non_differentiable(meta.lse, max_logits)
+    else:
+        ctx.mark_non_differentiable(meta.lse)
+    return (out[..., :d] if pad else out), meta.lse, max_logits
+
+
+def _index_attn_backward(ctx, dout, need_sink):
+    """backward shared by IndexAttnFunc and IndexAttnSinkFunc: (dq, dk, dv,
+    dsink) in the input dtypes, None where no gradient is needed"""
+    q, k, v, out, lse, indices_2d, sink = ctx.saved_tensors
+    in_dtype = q.dtype
+    d = q.shape[-1]
+    if in_dtype == torch.float8_e4m3fn:
+        pad = ctx.pad
+        q, k, v, dout = [
+            _pad_head_dim(t.to(torch.bfloat16), pad) for t in (q, k, v, dout)
+        ]
+    need_sink = need_sink and sink is not None
+    dq, dk, dv, dsink = _flex_flash_attn_backward_index(
+        dout, q, k, v, out, lse, indices_2d,
+        ctx.softmax_scale, ctx.softcap,
+        sink=sink if need_sink else None, sink_layout=ctx.sink_layout,
+    )
+    need_q, need_k, need_v = ctx.needs_input_grad[:3]
+    return (
+        dq[..., :d].to(in_dtype) if need_q else None,
+        dk[..., :d].to(in_dtype) if need_k else None,
+        dv[..., :d].to(in_dtype) if need_v else None,
+        dsink.to(sink.dtype) if need_sink else None,
+    )
 
 
 class IndexAttnFunc(torch.autograd.Function):
@@ -496,45 +591,47 @@ class IndexAttnFunc(torch.autograd.Function):
     kernels over upcast operands with the fp8 forward's out/lse, and the
     gradients are cast back to fp8 (the policy of FlexFlashAttnFunc.backward).
     An odd fp8 head dim is zero-padded here, not by the caller: the forward
-    pads the bytes and the backward pads the bf16 upcast."""
+    pads the bytes and the backward pads the bf16 upcast.
+
+    This is the node of a call without sink and max_logits (six inputs, out
+    and lse); IndexAttnSinkFunc below carries those two."""
 
     @staticmethod
     def forward(ctx, q, k, v, indices_2d, softmax_scale, softcap):
-        is_fp8 = q.dtype == torch.float8_e4m3fn
-        d = q.shape[-1]
-        pad = _index_head_dim_pad(d) if is_fp8 else 0
-        out, meta = _flex_flash_attn_forward_index(
-            _pad_head_dim(q, pad), _pad_head_dim(k, pad), _pad_head_dim(v, pad),
-            indices_2d, softmax_scale, softcap,
+        out, lse, _ = _index_attn_forward(
+            ctx, q, k, v, indices_2d, softmax_scale, softcap, None, "sh", False
         )
-        ctx.save_for_backward(q, k, v, out, meta.lse, indices_2d)
-        ctx.softmax_scale = softmax_scale
-        ctx.softcap = softcap
-        ctx.pad = pad
-        ctx.mark_non_differentiable(meta.lse)
-        return (out[..., :d] if pad else out), meta.lse
+        return out, lse
 
     @staticmethod
     def backward(ctx, dout, _dlse):
-        q, k, v, out, lse, indices_2d = ctx.saved_tensors
-        in_dtype = q.dtype
-        d = q.shape[-1]
-        if in_dtype == torch.float8_e4m3fn:
-            pad = ctx.pad
-            q, k, v, dout = [
-                _pad_head_dim(t.to(torch.bfloat16), pad) for t in (q, k, v, dout)
-            ]
-        dq, dk, dv = _flex_flash_attn_backward_index(
-            dout, q, k, v, out, lse, indices_2d,
-            ctx.softmax_scale, ctx.softcap,
+        dq, dk, dv, _ = _index_attn_backward(ctx, dout, False)
+        return dq, dk, dv, None, None, None
+
+
+class IndexAttnSinkFunc(torch.autograd.Function):
+    """IndexAttnFunc with an attention sink and/or max_logits. The forward
+    kernel folds the sink in; the saved lse is the sink-corrected one and the
+    saved out the sink-scaled one, so the dQ/dK/dV kernel needs nothing more,
+    and dsink comes from magi_ffa_dsink in f32 (for fp8 inputs too), returned
+    in the sink's dtype, None when the sink needs no gradient. Returns (out,
+    lse, max_logits); lse and max_logits are non-differentiable, max_logits
+    is None unless return_max_logits."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, indices_2d, softmax_scale, softcap,
+                sink, sink_layout, return_max_logits):
+        return _index_attn_forward(
+            ctx, q, k, v, indices_2d, softmax_scale, softcap,
+            sink, sink_layout, return_max_logits,
         )
-        need_q, need_k, need_v = ctx.needs_input_grad[:3]
-        return (
-            dq[..., :d].to(in_dtype) if need_q else None,
-            dk[..., :d].to(in_dtype) if need_k else None,
-            dv[..., :d].to(in_dtype) if need_v else None,
-            None, None, None,
+
+    @staticmethod
+    def backward(ctx, dout, *_):
+        dq, dk, dv, dsink = _index_attn_backward(
+            ctx, dout, ctx.needs_input_grad[6]
         )
+        return dq, dk, dv, None, None, None, dsink, None, None
 
 
 def _flex_flash_attn_backward(
@@ -780,7 +877,15 @@ def flex_flash_attn_func(
     reference is forward-only here): dK/dV are scattered with fp32 atomic
     adds, so deterministic=True is rejected when a gradient is needed.
     q/k/v may be all bf16 or all float8_e4m3fn (fp8 forward kernel, bf16 out,
-    bf16-upcast backward, fp8 gradients)."""
+    bf16-upcast backward, fp8 gradients).
+    sink / sink_layout and return_max_logits take effect on this path as on
+    the range path: the sink ("sh" [s_sink, hq] or "ssh" [total_q, s_sink,
+    hq], s_sink in [1, 8]) is folded into out and lse in the kernel's
+    epilogue (a token whose list is all -1 gets out = 0, lse = lse_sink) and
+    is differentiable (dsink in sink.dtype, f32 math, fp8 inputs included);
+    meta.max_logits is the per-head f32 [hq] maximum scaled (softcapped)
+    logit over valid slots (-inf if there is none), hq <= 128, and the sink
+    logits do not enter it."""
     # ── sparse-input validation (mirrors reference :1344-1384) ──
     _has_ranges = q_ranges is not None
     _has_index = index_attn_indices is not None
@@ -808,7 +913,7 @@ def flex_flash_attn_func(
         # the differentiable path is taken only when a gradient can flow; the
         # no-grad call below is the plain forward launch
         needs_grad = torch.is_grad_enabled() and any(
-            t.requires_grad for t in (q, k, v)
+            t is not None and t.requires_grad for t in (q, k, v, sink)
         )
         if needs_grad:
             assert q.is_cuda and k.is_cuda and v.is_cuda, (
@@ -823,15 +928,28 @@ def flex_flash_attn_func(
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
         indices_2d = index_attn_indices.reshape(-1, max_topk)
+        if return_max_logits:
+            assert q.shape[1] <= 128, "num_qheads must be <= 128 (reference cap)"
 
         def _index_call(q_, k_, v_):
             if needs_grad:
-                out_, lse_ = IndexAttnFunc.apply(
-                    q_, k_, v_, indices_2d, softmax_scale, softcap
+                if sink is None and not return_max_logits:
+                    out_, lse_ = IndexAttnFunc.apply(
+                        q_, k_, v_, indices_2d, softmax_scale, softcap
+                    )
+                    return out_, AttnForwardMeta(lse=lse_, max_logits=None)
+                out_, lse_, ml_ = IndexAttnSinkFunc.apply(
+                    q_, k_, v_, indices_2d, softmax_scale, softcap,
+                    sink, sink_layout, return_max_logits,
                 )
-                return out_, AttnForwardMeta(lse=lse_, max_logits=None)
+                return out_, AttnForwardMeta(lse=lse_, max_logits=ml_)
+            ml_ = None
+            if return_max_logits:
+                ml_ = torch.full((q_.shape[1],), float("-inf"),
+                                 dtype=torch.float32, device=q_.device)
             return _flex_flash_attn_forward_index(
-                q_, k_, v_, indices_2d, softmax_scale, softcap
+                q_, k_, v_, indices_2d, softmax_scale, softcap,
+                sink=sink, sink_layout=sink_layout, max_logits=ml_,
             )
 
         d = q.shape[-1]
