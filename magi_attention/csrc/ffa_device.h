@@ -1,12 +1,23 @@
-// ffa_device.h — device helpers shared by the FFA kernels (gfx950, wave64):
-// vector typedefs, the software-pipelined LDS-DMA barrier, the LDS-DMA issue
-// that bypasses the compiler's waitcnt tracking with its drain, and the MFMA
-// 32x32x16 fragment helpers. Included by ffa_fwd.hip, ffa_bwd.hip,
-// ffa_index.hip, ffa_index_bwd.hip, ffa_fwd_fp8.hip and ffa_index_fp8.hip;
-// everything here is force-inlined.
+// ffa_device.h — code shared by the FFA kernels (gfx950, wave64); the device
+// helpers are force-inlined. Sections, with the files that use them:
+//   pipeline    pipe_barrier, glds16_untracked, drain_vm, pin_vgpr
+//               (ffa_fwd, ffa_bwd)
+//   lanes       warp_xor32 (all kernels)
+//   index rows  index_valid_count (index forwards and backward),
+//               index_sink_lse, index_sink_fold, head_atomic_max
+//               (ffa_index, ffa_index_fp8)
+//   fragments   pack_bf16_pair, fast_exp2, crow, tr16_frag, cframe_to_afrag
+//               (the bf16 kernels), to_fp8, cframe_to_afrag_fp8 (the fp8 ones)
+//   softmax     FP8_MAX_OFFSET, softmax_step_fp8 (ffa_fwd_fp8, ffa_index_fp8)
+//   index host  IdxFwdParams<T>, index_fwd_entry: the one host path of
+//               magi_ffa_fwd_index and magi_ffa_fwd_index_fp8
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "../../include/magi_ffa.h"
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
@@ -62,6 +73,28 @@ DEV_INLINE void pin_vgpr(T& x) {
 }
 
 DEV_INLINE float warp_xor32(float v) { return __shfl_xor(v, 32, 64); }
+
+// ---- index rows ----
+
+// Valid count of an index row (ffa_index.hip, ffa_index_fp8.hip,
+// ffa_index_bwd.hip): the -1 padding is contiguous at the tail, so a
+// wave-uniform binary search (same address every lane -> broadcast loads)
+// finds it in log2(max_topk) dwords.
+DEV_INLINE int index_valid_count(const int* irow, int max_topk) {
+  int count = max_topk;
+  if (irow[max_topk - 1] < 0) {
+    int lo = 0, hic = max_topk - 1;
+    while (lo < hic) {
+      const int mid = (lo + hic) >> 1;
+      if (irow[mid] < 0)
+        hic = mid;
+      else
+        lo = mid + 1;
+    }
+    count = lo;
+  }
+  return count;
+}
 
 // ---- index-attention epilogue helpers (ffa_index.hip, ffa_index_fp8.hip) ----
 
@@ -213,4 +246,135 @@ DEV_INLINE long cframe_to_afrag_fp8(const float* val, int tt) {
   }
   auto r2 = __builtin_amdgcn_permlane32_swap(A.u, B.u, false, false);
   return ((long)(unsigned)r2[1] << 32) | (unsigned)r2[0];
+}
+
+// fp8 softmax offset in the exp2 domain (reference softmax.h:151): P =
+// exp2(t - m + 8) lands in [0, 256], inside the e4m3 range (max 448). l_run
+// and acc_o carry the 2^8; the epilogues subtract it from the lse again.
+constexpr float FP8_MAX_OFFSET = 8.f;
+
+// One online-softmax step of the fp8 forwards, swapped-QK layout: a lane owns
+// the 16 scores t[] of ONE q row (the other 16 sit in lane ^ 32), already
+// scaled into the exp2 domain, masked slots -inf; mx is their lane-local max.
+// Updates m_run, l_run and acc_o and leaves P in pr[] (a masked slot is
+// exactly 0).
+// No defer-max: a deferred maximum would let P exceed 256. The O rescale sits
+// under a wave-uniform condition: ds_bpermute reads other lanes' registers,
+// so every lane must be active whenever any lane needs it.
+template <int DT>
+DEV_INLINE void softmax_step_fp8(const float (&t)[16], float mx, int hi,
+                                 float& m_run, float& l_run,
+                                 f32x16 (&acc_o)[DT], float (&pr)[16]) {
+  mx = fmaxf(mx, warp_xor32(mx));
+  const float m_new = fmaxf(m_run, mx);
+  const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+  const float alpha = (m_run == -INFINITY) ? 0.f : fast_exp2(m_run - m_use);
+  m_run = m_new;
+
+  float psum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    pr[r] = fast_exp2(t[r] - m_use + FP8_MAX_OFFSET);
+    psum += pr[r];
+  }
+  l_run = l_run * alpha + (psum + warp_xor32(psum));
+
+  if (__any(alpha != 1.f)) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int src = crow(r, hi);
+      const float aq = __uint_as_float(
+          __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(alpha)));
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) acc_o[dt][r] *= aq;
+    }
+  }
+}
+
+// ---- index forward, host side (ffa_index.hip: T = bf16_t, ffa_index_fp8.hip:
+// T = unsigned char) ----
+
+template <class T>
+struct IdxFwdParams {
+  const T* q;
+  const T* k;
+  const T* v;
+  float* out_f32;    // used when OUT_BF16 == false
+  bf16_t* out_bf16;  // used when OUT_BF16 == true
+  float* lse;
+  const int* idx2d;  // [total_q, max_topk]
+  int max_topk;
+  int hq;
+  float scale;
+  float softcap;
+  long long total_q, total_k;
+  const float* sink;  // null = no sink
+  int s_sink;
+  int sink_ssh;
+  float* max_logits;  // [hq], null = off
+};
+
+// Body of magi_ffa_fwd_index / magi_ffa_fwd_index_fp8: checks, params, launch
+// shape and dispatch. launch(D, W, HAS_SOFTCAP, OUT_BF16, grid, block, stream,
+// p) gets the four template arguments as std::integral_constant values and
+// launches its kernel. Nothing before that call touches the HIP runtime.
+template <class T, class Launch>
+static int index_fwd_entry(const magi_ffa_index_args* a, Launch launch) {
+  if (!a || !a->q || !a->k || !a->v || !a->out || !a->lse || !a->indices_2d)
+    return -1;
+  if (a->d != 64 && a->d != 128) return -2;
+  if (a->hk != 1) return -3;  // kv heads are folded into K rows (magi_ffa.h)
+  if (a->max_topk <= 0 || (a->max_topk & 63) != 0) return -4;
+  if (a->sink && (a->s_sink < 1 || a->s_sink > 8)) return -5;
+  if (a->total_q <= 0 || a->hq <= 0) return 0;
+
+  IdxFwdParams<T> p;
+  p.q = (const T*)a->q;
+  p.k = (const T*)a->k;
+  p.v = (const T*)a->v;
+  p.out_f32 = (float*)a->out;
+  p.out_bf16 = (bf16_t*)a->out;
+  p.lse = a->lse;
+  p.idx2d = a->indices_2d;
+  p.max_topk = a->max_topk;
+  p.hq = a->hq;
+  p.scale = a->softmax_scale;
+  p.softcap = a->softcap;
+  p.total_q = a->total_q;
+  p.total_k = a->total_k;
+  p.sink = a->sink;
+  p.s_sink = a->s_sink;
+  p.sink_ssh = a->sink_ssh;
+  p.max_logits = a->max_logits;
+
+  // head-block = 32*W query heads; pick W so one wave-set covers hq (DiT
+  // ratio 128 -> 4 waves; small-ratio MHA shapes keep lanes busy at W=1)
+  const int w = (a->hq > 64) ? 4 : (a->hq > 32 ? 2 : 1);
+  const int span = 32 * w;
+  const dim3 grid((unsigned)a->total_q, (unsigned)((a->hq + span - 1) / span),
+                  1);
+  const dim3 block(64 * w);
+  const hipStream_t stream = (hipStream_t)a->stream;
+  const bool sc = a->softcap > 0.f;
+  const bool obf16 = !a->out_is_fp32;
+  auto with_dw = [&](auto D, auto W) {
+    auto go = [&](auto SC, auto OB) {
+      launch(D, W, SC, OB, grid, block, stream, p);
+    };
+    if (sc) {
+      if (obf16) go(std::true_type{}, std::true_type{});
+      else go(std::true_type{}, std::false_type{});
+    } else {
+      if (obf16) go(std::false_type{}, std::true_type{});
+      else go(std::false_type{}, std::false_type{});
+    }
+  };
+  auto with_d = [&](auto D) {
+    if (w == 4) with_dw(D, std::integral_constant<int, 4>{});
+    else if (w == 2) with_dw(D, std::integral_constant<int, 2>{});
+    else with_dw(D, std::integral_constant<int, 1>{});
+  };
+  if (a->d == 64) with_d(std::integral_constant<int, 64>{});
+  else with_d(std::integral_constant<int, 128>{});
+  return (int)hipGetLastError();
 }

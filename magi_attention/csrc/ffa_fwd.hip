@@ -326,31 +326,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
     // ---- P -> bf16 A-fragments (cvt_pk + permlane32_swap) ----
     bf16x8 pa[2];
 #pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-      unsigned c0 = pack_bf16_pair(pr[8 * tt + 0], pr[8 * tt + 1]);
-      unsigned c1 = pack_bf16_pair(pr[8 * tt + 2], pr[8 * tt + 3]);
-      unsigned c2 = pack_bf16_pair(pr[8 * tt + 4], pr[8 * tt + 5]);
-      unsigned c3 = pack_bf16_pair(pr[8 * tt + 6], pr[8 * tt + 7]);
-      {
-        auto r2 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
-        c0 = r2[0];
-        c2 = r2[1];
-      }
-      {
-        auto r2 = __builtin_amdgcn_permlane32_swap(c1, c3, false, false);
-        c1 = r2[0];
-        c3 = r2[1];
-      }
-      union {
-        unsigned u[4];
-        bf16x8 v;
-      } cvt;
-      cvt.u[0] = c0;
-      cvt.u[1] = c1;
-      cvt.u[2] = c2;
-      cvt.u[3] = c3;
-      pa[tt] = cvt.v;
-    }
+    for (int tt = 0; tt < 2; ++tt) pa[tt] = cframe_to_afrag(pr, tt);
 
     // ---- PV: B-frags via ds_read_b64_tr_b16 off the V row image ----
     {

@@ -71,7 +71,6 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
   const int qclamp = qvalid ? qrow : (qe - 1);
 
   const float sl2 = p.scale * 1.4426950408889634f;
-  constexpr float MAX_OFFSET = 8.f;  // reference softmax.h:151 fp8 offset
 
   int n_lo = ks, n_hi = ke;
   if (ke > ks && q0 < qe) {
@@ -212,33 +211,8 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
         mx = fmaxf(mx, t[r]);
       }
     }
-    mx = fmaxf(mx, warp_xor32(mx));
-
-    const float m_new = fmaxf(m_run, mx);
-    const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-    const float alpha = (m_run == -INFINITY) ? 0.f : fast_exp2(m_run - m_use);
-    m_run = m_new;
-
     float pr[16];
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      // fp8 convention: exp2 output in [0, 256] (max_offset = 8)
-      pr[r] = fast_exp2(t[r] - m_use + MAX_OFFSET);
-      psum += pr[r];
-    }
-    l_run = l_run * alpha + (psum + warp_xor32(psum));
-
-    if (__any(alpha != 1.f)) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int src = crow(r, hi);
-        const float aq = __uint_as_float(
-            __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(alpha)));
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) acc_o[dt][r] *= aq;
-      }
-    }
+    softmax_step_fp8(t, mx, hi, m_run, l_run, acc_o, pr);
 
     // ---- P -> fp8 A-fragments (pack 4 + ONE permlane swap per 16-k) ----
     long pa[2];
@@ -281,9 +255,9 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
     if (lane == 0 && ml != -INFINITY)
       unsafeAtomicMax(p.max_logits + h, ml);
   }
-  // ---- epilogue: fp8 sum is scaled by 2^MAX_OFFSET relative to exp2(t-m) ----
+  // ---- epilogue: fp8 sum is scaled by 2^FP8_MAX_OFFSET relative to exp2(t-m) ----
   const float lse_new = (l_run > 0.f)
-                            ? (m_run - MAX_OFFSET + __log2f(l_run)) *
+                            ? (m_run - FP8_MAX_OFFSET + __log2f(l_run)) *
                                   0.6931471805599453f
                             : -INFINITY;
   const float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;

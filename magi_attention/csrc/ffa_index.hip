@@ -43,28 +43,9 @@
 
 #define IDX_BN 32  // k rows per inner MFMA tile
 
-struct IdxParams {
-  const bf16_t* q;
-  const bf16_t* k;
-  const bf16_t* v;
-  float* out_f32;
-  bf16_t* out_bf16;
-  float* lse;
-  const int* idx2d;  // [total_q, max_topk]
-  int max_topk;
-  int hq;
-  float scale;
-  float softcap;
-  long long total_q, total_k;
-  const float* sink;  // null = no sink
-  int s_sink;
-  int sink_ssh;
-  float* max_logits;  // [hq], null = off
-};
-
 template <int D, bool HAS_SOFTCAP, bool OUT_BF16, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
-    IdxParams p) {
+    IdxFwdParams<bf16_t> p) {
   constexpr int DF = D / 16;
   constexpr int DT = D / 32;
 
@@ -76,22 +57,8 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
   const int lo32 = lane & 31;
   const int hi = lane >> 5;
 
-  // ---- valid-count: the -1 padding is contiguous at the tail, so a
-  // wave-uniform binary search (same address every lane -> broadcast loads)
-  // finds it in log2(max_topk) dwords ----
   const int* irow = p.idx2d + tok * (long long)p.max_topk;
-  int count = p.max_topk;
-  if (irow[p.max_topk - 1] < 0) {
-    int lo = 0, hic = p.max_topk - 1;
-    while (lo < hic) {
-      const int mid = (lo + hic) >> 1;
-      if (irow[mid] < 0)
-        hic = mid;
-      else
-        lo = mid + 1;
-    }
-    count = lo;
-  }
+  const int count = index_valid_count(irow, p.max_topk);
   if (__builtin_expect(count == 0, 0)) {
     // out zero-init + lse -inf preset by the host; with a sink the row's
     // softmax mass is the sink's alone: lse = lse_sink, out stays 0
@@ -259,31 +226,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     // ---- P -> bf16 A-fragments ----
     bf16x8 pa[2];
 #pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-      unsigned c0 = pack_bf16_pair(pr[8 * tt + 0], pr[8 * tt + 1]);
-      unsigned c1 = pack_bf16_pair(pr[8 * tt + 2], pr[8 * tt + 3]);
-      unsigned c2 = pack_bf16_pair(pr[8 * tt + 4], pr[8 * tt + 5]);
-      unsigned c3 = pack_bf16_pair(pr[8 * tt + 6], pr[8 * tt + 7]);
-      {
-        auto r2 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
-        c0 = r2[0];
-        c2 = r2[1];
-      }
-      {
-        auto r2 = __builtin_amdgcn_permlane32_swap(c1, c3, false, false);
-        c1 = r2[0];
-        c3 = r2[1];
-      }
-      union {
-        unsigned u[4];
-        bf16x8 v;
-      } cvt;
-      cvt.u[0] = c0;
-      cvt.u[1] = c1;
-      cvt.u[2] = c2;
-      cvt.u[3] = c3;
-      pa[tt] = cvt.v;
-    }
+    for (int tt = 0; tt < 2; ++tt) pa[tt] = cframe_to_afrag(pr, tt);
 
     // ---- PV ----
     {
@@ -365,70 +308,12 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
   }
 }
 
-// ------------------------------------------------------------------
-// launcher
-// ------------------------------------------------------------------
-template <int D, int W>
-static int launch_index_d(const magi_ffa_index_args* a, const IdxParams& p,
-                          dim3 grid, hipStream_t stream) {
-  const bool sc = a->softcap > 0.f;
-  const bool obf16 = !a->out_is_fp32;
-  dim3 block(64 * W);
-#define ILAUNCH(SC, OB)                                                      \
-  hipLaunchKernelGGL((ffa_index_fwd_kernel<D, SC, OB, W>), grid, block, 0, \
-                     stream, p)
-  if (sc) {
-    if (obf16) ILAUNCH(true, true);
-    else ILAUNCH(true, false);
-  } else {
-    if (obf16) ILAUNCH(false, true);
-    else ILAUNCH(false, false);
-  }
-#undef ILAUNCH
-  return (int)hipGetLastError();
-}
-
+// host entry: checks, params and dispatch are index_fwd_entry (ffa_device.h)
 extern "C" int magi_ffa_fwd_index(const magi_ffa_index_args* a) {
-  if (!a || !a->q || !a->k || !a->v || !a->out || !a->lse || !a->indices_2d)
-    return -1;
-  if (a->d != 64 && a->d != 128) return -2;
-  if (a->hk != 1) return -3;  // kv heads are folded into K rows (see header)
-  if (a->max_topk <= 0 || (a->max_topk & 63) != 0) return -4;
-  if (a->sink && (a->s_sink < 1 || a->s_sink > 8)) return -5;
-  if (a->total_q <= 0) return 0;
-
-  IdxParams p;
-  p.q = (const bf16_t*)a->q;
-  p.k = (const bf16_t*)a->k;
-  p.v = (const bf16_t*)a->v;
-  p.out_f32 = (float*)a->out;
-  p.out_bf16 = (bf16_t*)a->out;
-  p.lse = a->lse;
-  p.idx2d = a->indices_2d;
-  p.max_topk = a->max_topk;
-  p.hq = a->hq;
-  p.scale = a->softmax_scale;
-  p.softcap = a->softcap;
-  p.total_q = a->total_q;
-  p.total_k = a->total_k;
-  p.sink = a->sink;
-  p.s_sink = a->s_sink;
-  p.sink_ssh = a->sink_ssh;
-  p.max_logits = a->max_logits;
-
-  // head-block = 32*W query heads; pick W so one wave-set covers hq (DiT
-  // ratio 128 -> 4 waves; small-ratio MHA shapes keep lanes busy at W=1)
-  int w = (a->hq > 64) ? 4 : (a->hq > 32 ? 2 : 1);
-  const int span = 32 * w;
-  const unsigned hblocks = (unsigned)((a->hq + span - 1) / span);
-  dim3 grid((unsigned)a->total_q, hblocks, 1);
-  hipStream_t stream = (hipStream_t)a->stream;
-  if (a->d == 64) {
-    if (w == 4) return launch_index_d<64, 4>(a, p, grid, stream);
-    if (w == 2) return launch_index_d<64, 2>(a, p, grid, stream);
-    return launch_index_d<64, 1>(a, p, grid, stream);
-  }
-  if (w == 4) return launch_index_d<128, 4>(a, p, grid, stream);
-  if (w == 2) return launch_index_d<128, 2>(a, p, grid, stream);
-  return launch_index_d<128, 1>(a, p, grid, stream);
+  return index_fwd_entry<bf16_t>(
+      a, [](auto D, auto W, auto SC, auto OB, dim3 grid, dim3 block,
+            hipStream_t stream, const IdxFwdParams<bf16_t>& p) {
+        hipLaunchKernelGGL((ffa_index_fwd_kernel<D(), SC(), OB(), W()>), grid,
+                           block, 0, stream, p);
+      });
 }

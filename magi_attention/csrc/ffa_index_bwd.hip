@@ -73,20 +73,8 @@ __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
   const int lo32 = lane & 31;
   const int hi = lane >> 5;
 
-  // ---- valid-count (same wave-uniform binary search as the forward) ----
   const int* irow = p.idx2d + tok * (long long)p.max_topk;
-  int count = p.max_topk;
-  if (irow[p.max_topk - 1] < 0) {
-    int lo = 0, hic = p.max_topk - 1;
-    while (lo < hic) {
-      const int mid = (lo + hic) >> 1;
-      if (irow[mid] < 0)
-        hic = mid;
-      else
-        lo = mid + 1;
-    }
-    count = lo;
-  }
+  const int count = index_valid_count(irow, p.max_topk);
   if (count == 0) return;  // dq zero-init by the host; no dk/dv contribution
 
   const int q0 = h0 + wave * 32;  // first query head of this wave
@@ -397,7 +385,7 @@ extern "C" int magi_ffa_bwd_index(const magi_ffa_index_bwd_args* a) {
   p.total_q = a->total_q;
   p.total_k = a->total_k;
 
-  // head-block = 32*W query heads, chosen as in the forward launcher
+  // head-block = 32*W query heads, the rule of index_fwd_entry (ffa_device.h)
   const int w = (a->hq > 64) ? 4 : (a->hq > 32 ? 2 : 1);
   const int span = 32 * w;
   const unsigned hblocks = (unsigned)((a->hq + span - 1) / span);

@@ -8,7 +8,7 @@
 //     returns at once (host presets out = 0, lse = -inf); direct epilogue.
 //   - Q, K, V are raw e4m3 bytes, no descale factors. S = K Q^T and P V run
 //     on v_mfma_f32_32x32x16_fp8_fp8 (fp32 accumulate); online softmax in the
-//     exp2 domain with MAX_OFFSET = 8 subtracted before exp2 (P in [0, 256],
+//     exp2 domain with FP8_MAX_OFFSET = 8 subtracted before exp2 (P in [0, 256],
 //     inside the e4m3 range) and added back into the lse; P is packed to e4m3
 //     in-register. No defer-max: a deferred maximum would let P exceed 256.
 //
@@ -53,35 +53,15 @@ using u8 = unsigned char;
 using u8x16 = __attribute__((ext_vector_type(16))) u8;
 using i64x2 = __attribute__((ext_vector_type(2))) long;
 
-struct Idx8Params {
-  const u8* q;
-  const u8* k;
-  const u8* v;
-  float* out_f32;
-  bf16_t* out_bf16;
-  float* lse;
-  const int* idx2d;  // [total_q, max_topk]
-  int max_topk;
-  int hq;
-  float scale;
-  float softcap;
-  long long total_q, total_k;
-  const float* sink;  // null = no sink
-  int s_sink;
-  int sink_ssh;
-  float* max_logits;  // [hq], null = off
-};
-
 // Register budget: the D=128 instances need ~180 registers (64 accumulator +
 // the exp2/pack working set + the V rows in flight), so they ask for 2
 // waves/SIMD (256 registers); a 4 waves/SIMD bound (128) spills. D=64 fits
 // 128 registers at 2 and 4 waves per workgroup.
 template <int D, bool HAS_SOFTCAP, bool OUT_BF16, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, (D > 64 || WAVES < 2) ? 2 : 4) void
-ffa_index_fwd_fp8_kernel(Idx8Params p) {
+ffa_index_fwd_fp8_kernel(IdxFwdParams<u8> p) {
   constexpr int DF = D / 16;  // 16-deep MFMAs per QK chain
   constexpr int DT = D / 32;
-  constexpr float MAX_OFFSET = 8.f;  // fp8 softmax offset (ffa_fwd_fp8.hip)
 
   const long long tok = blockIdx.x;
   const int h0 = blockIdx.y * (32 * WAVES);
@@ -91,20 +71,8 @@ ffa_index_fwd_fp8_kernel(Idx8Params p) {
   const int lo32 = lane & 31;
   const int hi = lane >> 5;
 
-  // ---- valid-count: wave-uniform binary search over the -1 tail ----
   const int* irow = p.idx2d + tok * (long long)p.max_topk;
-  int count = p.max_topk;
-  if (irow[p.max_topk - 1] < 0) {
-    int lo = 0, hic = p.max_topk - 1;
-    while (lo < hic) {
-      const int mid = (lo + hic) >> 1;
-      if (irow[mid] < 0)
-        hic = mid;
-      else
-        lo = mid + 1;
-    }
-    count = lo;
-  }
+  const int count = index_valid_count(irow, p.max_topk);
   if (__builtin_expect(count == 0, 0)) {
     // out zero-init + lse -inf preset by the host; with a sink the row's
     // softmax mass is the sink's alone: lse = lse_sink, out stays 0
@@ -236,34 +204,8 @@ ffa_index_fwd_fp8_kernel(Idx8Params p) {
         mx = fmaxf(mx, t[r]);
       }
     }
-    mx = fmaxf(mx, warp_xor32(mx));
-
-    const float m_new = fmaxf(m_run, mx);
-    const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-    const float alpha = (m_run == -INFINITY) ? 0.f : fast_exp2(m_run - m_use);
-    m_run = m_new;
-
     float pr[16];
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      // fp8 convention: exp2 output in [0, 256] (max_offset = 8); a masked
-      // slot is exp2(-inf) = 0 exactly
-      pr[r] = fast_exp2(t[r] - m_use + MAX_OFFSET);
-      psum += pr[r];
-    }
-    l_run = l_run * alpha + (psum + warp_xor32(psum));
-
-    if (__any(alpha != 1.f)) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int src = crow(r, hi);
-        const float aq = __uint_as_float(
-            __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(alpha)));
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) acc_o[dt][r] *= aq;
-      }
-    }
+    softmax_step_fp8(t, mx, hi, m_run, l_run, acc_o, pr);
 
     // ---- P -> fp8 A-fragments, PV from the byte-transposed V tile ----
     long pa[2];
@@ -302,10 +244,10 @@ ffa_index_fwd_fp8_kernel(Idx8Params p) {
   }
 
   // ======================= epilogue (direct store) =======================
-  // the fp8 sum is scaled by 2^MAX_OFFSET relative to exp2(t - m)
+  // the fp8 sum is scaled by 2^FP8_MAX_OFFSET relative to exp2(t - m)
   float lse_new =
       (l_run > 0.f)
-          ? (m_run - MAX_OFFSET + __log2f(l_run)) * 0.6931471805599453f
+          ? (m_run - FP8_MAX_OFFSET + __log2f(l_run)) * 0.6931471805599453f
           : -INFINITY;
   float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
 
@@ -316,7 +258,7 @@ ffa_index_fwd_fp8_kernel(Idx8Params p) {
   if (p.max_logits && qvalid && hi == 0)
     head_atomic_max(p.max_logits + qh, m_run * 0.6931471805599453f);
   // sink fold, fp32, ahead of the single rounding of out. lse_new has left
-  // the 2^MAX_OFFSET domain above; inv_l still carries it (as l_run does) and
+  // the 2^FP8_MAX_OFFSET domain above; inv_l still carries it (as l_run does) and
   // only takes the extra factor exp(lse - lse'). Block-uniform branch; a null
   // sink leaves both untouched.
   if (p.sink && qvalid)
@@ -345,71 +287,12 @@ ffa_index_fwd_fp8_kernel(Idx8Params p) {
   }
 }
 
-// ------------------------------------------------------------------
-// launcher
-// ------------------------------------------------------------------
-template <int D, int W>
-static int launch_index8_d(const magi_ffa_index_args* a, const Idx8Params& p,
-                           dim3 grid, hipStream_t stream) {
-  const bool sc = a->softcap > 0.f;
-  const bool obf16 = !a->out_is_fp32;
-  dim3 block(64 * W);
-#define ILAUNCH(SC, OB)                                                        \
-  hipLaunchKernelGGL((ffa_index_fwd_fp8_kernel<D, SC, OB, W>), grid, block, 0, \
-                     stream, p)
-  if (sc) {
-    if (obf16) ILAUNCH(true, true);
-    else ILAUNCH(true, false);
-  } else {
-    if (obf16) ILAUNCH(false, true);
-    else ILAUNCH(false, false);
-  }
-#undef ILAUNCH
-  return (int)hipGetLastError();
-}
-
+// host entry: checks, params and dispatch are index_fwd_entry (ffa_device.h)
 extern "C" int magi_ffa_fwd_index_fp8(const magi_ffa_index_args* a) {
-  // validation order and codes of magi_ffa_fwd_index; nothing before the
-  // launch touches the HIP runtime
-  if (!a || !a->q || !a->k || !a->v || !a->out || !a->lse || !a->indices_2d)
-    return -1;
-  if (a->d != 64 && a->d != 128) return -2;
-  if (a->hk != 1) return -3;  // kv heads are folded into K rows (see header)
-  if (a->max_topk <= 0 || (a->max_topk & 63) != 0) return -4;
-  if (a->sink && (a->s_sink < 1 || a->s_sink > 8)) return -5;
-  if (a->total_q <= 0 || a->hq <= 0) return 0;
-
-  Idx8Params p;
-  p.q = (const u8*)a->q;
-  p.k = (const u8*)a->k;
-  p.v = (const u8*)a->v;
-  p.out_f32 = (float*)a->out;
-  p.out_bf16 = (bf16_t*)a->out;
-  p.lse = a->lse;
-  p.idx2d = a->indices_2d;
-  p.max_topk = a->max_topk;
-  p.hq = a->hq;
-  p.scale = a->softmax_scale;
-  p.softcap = a->softcap;
-  p.total_q = a->total_q;
-  p.total_k = a->total_k;
-  p.sink = a->sink;
-  p.s_sink = a->s_sink;
-  p.sink_ssh = a->sink_ssh;
-  p.max_logits = a->max_logits;
-
-  // head-block = 32*W query heads, chosen from hq as magi_ffa_fwd_index does
-  int w = (a->hq > 64) ? 4 : (a->hq > 32 ? 2 : 1);
-  const int span = 32 * w;
-  const unsigned hblocks = (unsigned)((a->hq + span - 1) / span);
-  dim3 grid((unsigned)a->total_q, hblocks, 1);
-  hipStream_t stream = (hipStream_t)a->stream;
-  if (a->d == 64) {
-    if (w == 4) return launch_index8_d<64, 4>(a, p, grid, stream);
-    if (w == 2) return launch_index8_d<64, 2>(a, p, grid, stream);
-    return launch_index8_d<64, 1>(a, p, grid, stream);
-  }
-  if (w == 4) return launch_index8_d<128, 4>(a, p, grid, stream);
-  if (w == 2) return launch_index8_d<128, 2>(a, p, grid, stream);
-  return launch_index8_d<128, 1>(a, p, grid, stream);
+  return index_fwd_entry<u8>(
+      a, [](auto D, auto W, auto SC, auto OB, dim3 grid, dim3 block,
+            hipStream_t stream, const IdxFwdParams<u8>& p) {
+        hipLaunchKernelGGL((ffa_index_fwd_fp8_kernel<D(), SC(), OB(), W()>),
+                           grid, block, 0, stream, p);
+      });
 }

@@ -90,9 +90,15 @@ def test_index_sink_older_codes_win():
             (dict(hk=2, max_topk=50), -3),
             (dict(max_topk=50, total_q=0), -4),
             (dict(total_q=0), -5),
+            (dict(hq=0), -5),
         ):
             a = _args(**over, **bad_sink)
             assert fn(ctypes.byref(a)) == code, over
+        # hq == 0 is an empty problem like total_q <= 0: after every
+        # validation code it returns 0 without a launch (total_q stays 8)
+        assert fn(ctypes.byref(_args(hq=0))) == 0
+        assert fn(ctypes.byref(_args(hq=0, sink=1, s_sink=8, max_logits=1))) == 0
+        assert fn(ctypes.byref(_args(hq=0, max_topk=50))) == -4
 
 
 @pytest.mark.parametrize("s_sink", [0, 1, 8, 9, -1, 1 << 20])
