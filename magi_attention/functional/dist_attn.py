@@ -27,6 +27,8 @@ from ..comm.primitive import (
     hier_group_reduce,
 )
 from ..meta.containers import AttnArg, CalcMeta, CommMeta, QoCommMeta
+from . import _ffa_launch
+from .flex_flash_attn import _flex_flash_attn_forward
 
 # test-only hook: lets CPU (gloo) tests run the runtime with an oracle
 # attention implementation. NEVER set in production; the product path on GPU
@@ -124,10 +126,8 @@ class DistAttnRuntime:
         lse_acc = torch.full(
             (tq, hq), float("-inf"), dtype=torch.float32, device=q.device
         )
-        max_logits = None
-        if return_max_logits:
-            max_logits = torch.full((hq,), float("-inf"), dtype=torch.float32,
-                                    device=q.device)
+        max_logits = (_ffa_launch.new_max_logits(hq, q.device)
+                      if return_max_logits else None)
 
         if self.qo_meta is not None:
             # QO-comm: cast q to the K-hosts, compute partial (out,lse) for
@@ -204,10 +204,8 @@ class DistAttnRuntime:
             out_acc.mul_(w.unsqueeze(-1).to(out_acc.dtype))
             lse_acc.copy_(lse_new.to(lse_acc.dtype))
             return
-        from .flex_flash_attn import _apply_sink_postprocess
-
-        tq, hq, d = out_acc.shape
-        _apply_sink_postprocess(out_acc, lse_acc, sink, "sh", tq, hq, d)
+        _ffa_launch._apply_sink_postprocess(out_acc, lse_acc, sink, "sh",
+                                            *out_acc.shape)
 
     def _fwd_partial(self, q, k, v, arg: AttnArg, out_acc, lse_acc, scale,
                      softcap=0.0, max_logits=None):
@@ -217,8 +215,6 @@ class DistAttnRuntime:
             _test_attn_backend.fwd_partial(q, k, v, arg, out_acc, lse_acc,
                                            scale, softcap, max_logits)
             return
-        from .flex_flash_attn import _flex_flash_attn_forward
-
         qr, kr, tm = arg.to_device(q.device)
         qk_starts = None
         if (env.is_auto_range_merge_enable()
@@ -255,15 +251,8 @@ class DistAttnRuntime:
         L = k.shape[0]
         scale = softmax_scale or self.softmax_scale or d ** (-0.5)
         in_dtype = q.dtype
-        if in_dtype == torch.float8_e4m3fn:
-            # mixed-precision policy (single-GPU wrapper, flex_flash_attn.py
-            # :521): backward runs the bf16 kernels over upcast operands
-            q = q.bfloat16()
-            k = k.bfloat16()
-            v = v.bfloat16()
-            dout = dout.bfloat16()
-            if out.dtype == torch.float8_e4m3fn:
-                out = out.bfloat16()
+        # same fp8 backward policy as the single-GPU wrapper
+        q, k, v, out, dout = _ffa_launch.upcast_fp8(q, k, v, out, dout)
 
         dq_acc = torch.zeros(tq, hq, d, dtype=torch.float32, device=q.device)
         dkv_acc = torch.zeros(2 * L, *k.shape[1:], dtype=torch.float32,
@@ -379,37 +368,13 @@ class DistAttnRuntime:
             return (-(p * dpsum.double().t().unsqueeze(0)).sum(-1)).to(
                 torch.float32
             )
-        from .. import _ffa_lib
-        from .._ffa_lib import MagiSinkArgs, check, current_stream_ptr, ptr
-
-        tq, hq = lse.shape
-        sink_f = sink.contiguous().float()
-        dsink = torch.zeros_like(sink_f)
-        sargs = MagiSinkArgs(
-            lse=ptr(lse), sink=ptr(sink_f), dsink=ptr(dsink), dpsum=ptr(dpsum),
-            total_rows=tq, n_heads=hq, d=0, s_sink=sink_f.shape[0], ssh=0,
-            stream=current_stream_ptr(),
-        )
-        check(_ffa_lib.lib().magi_ffa_dsink(sargs), "magi_ffa_dsink[dist]")
-        return dsink
+        sink_f, s_sink = _ffa_launch._check_sink(sink, "sh", *lse.shape)
+        return _ffa_launch.bwd_dsink(sink_f, s_sink, False, lse, dpsum)
 
     def _bwd_dpsum(self, dout, out):
         if _test_attn_backend is not None and not dout.is_cuda:
             return (dout.float() * out.float()).sum(-1)
-        from .. import _ffa_lib
-        from .._ffa_lib import MagiFfaBwdArgs, check, current_stream_ptr, ptr
-
-        tq, hq, d = dout.shape
-        dpsum = torch.empty(tq, hq, dtype=torch.float32, device=dout.device)
-        args = MagiFfaBwdArgs(
-            dout=ptr(dout.contiguous()), out=ptr(out.contiguous()),
-            dpsum=ptr(dpsum),
-            total_q=tq, hq=hq, d=d,
-            out_is_fp32=int(out.dtype == torch.float32),
-            stream=current_stream_ptr(),
-        )
-        check(_ffa_lib.lib().magi_ffa_bwd_preprocess(args), "bwd_preprocess")
-        return dpsum
+        return _ffa_launch.bwd_dpsum(dout, out)
 
     def _bwd_partial(self, dout, q, k, v, out, lse, dpsum, arg: AttnArg,
                      dq, dk, dv, scale, softcap=0.0):
@@ -420,35 +385,23 @@ class DistAttnRuntime:
                 dout, q, k, v, out, lse, dpsum, arg, dq, dk, dv, scale, softcap
             )
             return
-        from .. import _ffa_lib
-        from .._ffa_lib import MagiFfaBwdArgs, check, current_stream_ptr, ptr
-
         qr, kr, tm = arg.to_device(q.device)
-        tq, hq, d = q.shape
-        tk, hk, _ = k.shape
-        max_k = int(max(b - a for a, b in arg.k_ranges))
-        args = MagiFfaBwdArgs(
-            dout=ptr(dout), q=ptr(q), k=ptr(k.contiguous()),
-            v=ptr(v.contiguous()), out=ptr(out), lse=ptr(lse),
-            dq=ptr(dq), dk=ptr(dk), dv=ptr(dv), dpsum=ptr(dpsum),
-            q_ranges=ptr(qr), k_ranges=ptr(kr), attn_type_map=ptr(tm),
-            n_ranges=qr.shape[0], total_q=tq, total_k=tk,
-            hq=hq, hk=hk, d=d, max_seqlen_k=max_k,
-            out_is_fp32=int(out.dtype == torch.float32),
+        deterministic = env.is_deterministic_mode_enable()
+        args = _ffa_launch.bwd_args(
+            dout, out, dpsum, q=q, k=k.contiguous(), v=v.contiguous(),
+            lse=lse, dq=dq, dk=dk, dv=dv,
+            q_ranges=qr, k_ranges=kr, attn_type_map=tm,
+            # host-side ranges: no device sync
+            max_seqlen_k=int(max(b - a for a, b in arg.k_ranges)),
             softmax_scale=scale, softcap=softcap,
-            cu_margin=(env.ffa_backward_sm_margin()
+            sm_margin=(env.ffa_backward_sm_margin()
                        if dist.get_world_size(self.cp_group) > 1 else 0),
-            stream=current_stream_ptr(),
         )
-        from .flex_flash_attn import run_bwd_deterministic, run_bwd_passes
-
-        if env.is_deterministic_mode_enable():
-            run_bwd_deterministic(args, qr, kr, tm, hq, hk, q.device)
-        elif env.is_auto_range_merge_enable():
-            dq_t, dkv_t = arg.to_device_merged(q.device)
-            run_bwd_passes(args, q.device, dq_tables=dq_t, dkv_tables=dkv_t)
-        else:
-            run_bwd_passes(args, q.device)
+        merged = (arg.to_device_merged(q.device)
+                  if env.is_auto_range_merge_enable() and not deterministic
+                  else None)
+        _ffa_launch.run_bwd(args, qr, kr, tm, q.device,
+                            deterministic=deterministic, merged=merged)
 
 
 class DistAttnFunc(torch.autograd.Function):

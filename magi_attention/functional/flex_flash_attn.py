@@ -1,122 +1,26 @@
-# Reference surface: magi_attention/functional/flex_flash_attn.py
-# (_flex_flash_attn_forward:334, _flex_flash_attn_backward:594,
-#  FlexFlashAttnFunc:699, flex_flash_attn_func:1066).
-# MI355X-native rebuild: the JIT'd CUDA module is replaced by the C-ABI HIP
-# library (include/magi_ffa.h) bound via ctypes in magi_attention/_ffa_lib.py.
+# Single-GPU flex-flash-attention. Reference surface:
+# magi_attention/functional/flex_flash_attn.py (merge_ranges:79,
+# _flex_flash_attn_forward:334, _flex_flash_attn_backward:594,
+# FlexFlashAttnFunc:699, flex_flash_attn_func:1066).
+# MI355X-native: the JIT'd CUDA module is replaced by the C-ABI HIP library.
+# This file validates, allocates and wires autograd; _ffa_launch.py launches.
 from __future__ import annotations
 
-import ctypes
-import math
+import contextlib
 from typing import Optional, Tuple
 
 import torch
 
-_side_stream: dict = {}
-
-
-def _get_side_stream(device) -> torch.cuda.Stream:
-    key = device.index or 0
-    if key not in _side_stream:
-        _side_stream[key] = torch.cuda.Stream(device=device)
-    return _side_stream[key]
-
-
-def run_bwd_deterministic(args, q_ranges, k_ranges, attn_type_map,
-                          hq, hk, device) -> None:
-    """Deterministic backward: sequential launches over q-disjoint groups
-    (dq pass), k-disjoint groups x GQA head sub-launches (dkv pass) — every
-    accumulator element receives its additions in a fixed, stream-ordered
-    sequence."""
-    lib = _ffa_lib.lib()
-    gqa = hq // hk
-    q_groups = _color_ranges(q_ranges.cpu().tolist())
-    k_groups = _color_ranges(k_ranges.cpu().tolist())
-    base_margin = args.cu_margin & 0xFFFF
-
-    keep = []
-
-    def launch(fn, groups, ranges_pairs, what, head_splits=1):
-        for g in groups:
-            idx = torch.tensor(g, dtype=torch.long, device=device)
-            sq = _subset(ranges_pairs[0], idx)
-            sk = _subset(ranges_pairs[1], idx)
-            st = _subset(attn_type_map, idx)
-            keep.append((sq, sk, st))  # outlive the async launches
-            args.q_ranges = ptr(sq)
-            args.k_ranges = ptr(sk)
-            args.attn_type_map = ptr(st)
-            args.n_ranges = len(g)
-            for j in range(head_splits):
-                if head_splits > 1:
-                    args.cu_margin = base_margin | (gqa << 24) | (j << 16)
-                check(fn(args), what)
-            args.cu_margin = base_margin
-
-    launch(lib.magi_ffa_bwd_dq, q_groups, (q_ranges, k_ranges), "bwd_dq[det]")
-    hs = gqa if gqa > 1 else 1
-    if env.is_bwd_split_dkv(args.max_seqlen_k, args.d):
-        launch(lib.magi_ffa_bwd_dv, k_groups, (q_ranges, k_ranges),
-               "bwd_dv[det]", head_splits=hs)
-        launch(lib.magi_ffa_bwd_dk, k_groups, (q_ranges, k_ranges),
-               "bwd_dk[det]", head_splits=hs)
-    else:
-        launch(lib.magi_ffa_bwd_dkv, k_groups, (q_ranges, k_ranges),
-               "bwd_dkv[det]", head_splits=hs)
-
-
-def run_bwd_passes(args, device, dq_tables=None, dkv_tables=None) -> None:
-    """Launch the independent backward passes (dq / fused-dkv by default;
-    dq / dv / dk with MAGI_BWD_SPLIT_DKV=1) on two streams so their waves
-    co-schedule across the chip. dq_tables / dkv_tables override the range
-    tables per pass for auto_range_merge: (ranges_outer, ranges_inner,
-    attn_type_map, seg_starts) — outer = the pass's OWN loop dim."""
-    lib = _ffa_lib.lib()
-    main = torch.cuda.current_stream(device)
-    cosched = env.is_bwd_cosched()
-    side = _get_side_stream(device) if cosched else main
-    if cosched:
-        ev = torch.cuda.Event()
-        ev.record(main)          # dpsum + inputs ready
-        side.wait_event(ev)
-    keep = (dq_tables, dkv_tables)  # outlive the async launches
-
-    def set_tables(t, outer_is_q):
-        if t is None:
-            args.seg_starts = None
-            return
-        outer, inner, tm, starts = t
-        args.q_ranges = ptr(outer if outer_is_q else inner)
-        args.k_ranges = ptr(inner if outer_is_q else outer)
-        args.attn_type_map = ptr(tm)
-        args.seg_starts = ptr(starts)
-
-    args.stream = ctypes.c_void_p(side.cuda_stream)
-    set_tables(dq_tables, True)
-    check(lib.magi_ffa_bwd_dq(args), "magi_ffa_bwd_dq")
-    args.stream = ctypes.c_void_p(main.cuda_stream)
-    set_tables(dkv_tables, False)
-    if env.is_bwd_split_dkv(args.max_seqlen_k, args.d):
-        check(lib.magi_ffa_bwd_dv(args), "magi_ffa_bwd_dv")
-        check(lib.magi_ffa_bwd_dk(args), "magi_ffa_bwd_dk")
-    else:
-        check(lib.magi_ffa_bwd_dkv(args), "magi_ffa_bwd_dkv")
-    if cosched:
-        ev2 = torch.cuda.Event()
-        ev2.record(side)
-        main.wait_event(ev2)
-    del keep
-
-from .. import _ffa_lib, env
-from .._ffa_lib import (
-    MagiFfaBwdArgs,
-    MagiFfaFwdArgs,
-    check,
-    current_stream_ptr,
-    ptr,
-)
+from .. import magi_attn_ext
 from ..common.forward_meta import AttnForwardMeta
-
-import contextlib
+from . import _ffa_launch
+from ._ffa_launch import (  # noqa: F401  (re-exported: tests and tools import them here)
+    _apply_sink_postprocess,
+    _check_sink,
+    maybe_contiguous,
+    run_bwd_deterministic,
+    run_bwd_passes,
+)
 
 
 @contextlib.contextmanager
@@ -126,8 +30,6 @@ def maybe_profile_ffa_ctx(name: str, enable: bool = False):
     if not enable:
         yield
         return
-    from .. import magi_attn_ext
-
     magi_attn_ext.start_event(name)
     try:
         yield
@@ -144,8 +46,6 @@ def merge_ranges(
     flex_flash_attn.py:79 merge_ranges, built on the magi_attn_ext ops).
     Returns (merged_outer [n,2] zero-padded, sorted_outer, sorted_inner,
     sorted_attn_type_map, range_map inverse indices, unique_count [1])."""
-    from .. import magi_attn_ext
-
     idx = magi_attn_ext.argsort_ranges(outer_ranges)
     so, si, st = magi_attn_ext.reorder_ranges_and_attn_type_maps(
         outer_ranges, inner_ranges, attn_type_map, idx
@@ -167,12 +67,17 @@ def _seg_starts(inverse: torch.Tensor, n: int) -> torch.Tensor:
     return starts
 
 
+def _merged_tables(outer_ranges, inner_ranges, attn_type_map) -> tuple:
+    """A kernel's range tables under auto_range_merge: (unique outer ranges,
+    inner ranges, attn_type_map, segment starts), outer = its OWN loop dim."""
+    merged, _, inner, tm, inverse, _ = merge_ranges(
+        outer_ranges, inner_ranges, attn_type_map
+    )
+    return merged, inner, tm, _seg_starts(inverse, outer_ranges.shape[0])
+
+
 LOCK_GRAN = 128
 _lock_cache: dict[tuple[int, int], torch.Tensor] = {}
-
-
-def maybe_contiguous(x: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    return x.contiguous() if x is not None and not x.is_contiguous() else x
 
 
 def _get_locks(total_q: int, hq: int, device: torch.device) -> torch.Tensor:
@@ -192,33 +97,6 @@ def _max_seqlen_of(ranges: torch.Tensor) -> int:
     if ranges.numel() == 0:
         return 0
     return int((ranges[:, 1] - ranges[:, 0]).amax().item())
-
-
-def _color_ranges(ranges: list) -> list:
-    """Greedy interval partitioning: split slice indices into groups whose
-    ranges are pairwise DISJOINT. Deterministic mode runs one kernel launch
-    per group, sequentially on the stream, so reduction order is fixed by
-    construction — placement-independent, unlike device-side lock ordering
-    (the reference's deterministic.h approach assumes dispatch order, which
-    CDNA4 does not guarantee)."""
-    order = sorted(range(len(ranges)), key=lambda i: (ranges[i][0], ranges[i][1]))
-    groups: list = []   # list of (last_end, [indices])
-    for i in order:
-        s_, e_ = ranges[i]
-        placed = False
-        for g in groups:
-            if g[0] <= s_:
-                g[1].append(i)
-                g[0] = e_
-                placed = True
-                break
-        if not placed:
-            groups.append([e_, [i]])
-    return [sorted(g[1]) for g in groups]
-
-
-def _subset(t: Optional[torch.Tensor], idx: torch.Tensor) -> Optional[torch.Tensor]:
-    return None if t is None else t.index_select(0, idx)
 
 
 def _flex_flash_attn_forward(
@@ -253,13 +131,11 @@ def _flex_flash_attn_forward(
         "flex_flash_attn q, k and v must all be fp8-e4m3 or all be bf16, got "
         f"q={q.dtype}, k={k.dtype}, v={v.dtype}"
     )
-    q, k, v, q_ranges, k_ranges = [
-        maybe_contiguous(x) for x in (q, k, v, q_ranges, k_ranges)
-    ]
-    attn_type_map = maybe_contiguous(attn_type_map)
+    q, k, v, q_ranges, k_ranges, attn_type_map = map(
+        maybe_contiguous, (q, k, v, q_ranges, k_ranges, attn_type_map)
+    )
 
     tq, hq, d = q.shape
-    tk, hk, _ = k.shape
 
     if out is None:
         dtype = out_type or (q.dtype if disable_fwd_atomic_reduction else torch.float32)
@@ -278,20 +154,6 @@ def _flex_flash_attn_forward(
     if max_seqlen_q is None:
         max_seqlen_q = _max_seqlen_of(q_ranges)
 
-    args = MagiFfaFwdArgs(
-        q=ptr(q), k=ptr(k), v=ptr(v), out=ptr(out), lse=ptr(lse),
-        q_ranges=ptr(q_ranges), k_ranges=ptr(k_ranges),
-        attn_type_map=ptr(attn_type_map), locks=ptr(locks),
-        max_logits=ptr(max_logits), qk_starts=ptr(qk_starts),
-        n_ranges=q_ranges.shape[0], total_q=tq, total_k=tk,
-        hq=hq, hk=hk, d=d, max_seqlen_q=max_seqlen_q,
-        softmax_scale=softmax_scale, softcap=softcap,
-        out_is_fp32=int(out_is_fp32),
-        disable_atomic_reduction=int(disable_fwd_atomic_reduction),
-        cu_margin=sm_margin, stream=current_stream_ptr(),
-    )
-    fwd_fn = (_ffa_lib.lib().magi_ffa_fwd_fp8 if is_fp8
-              else _ffa_lib.lib().magi_ffa_fwd)
     if is_fp8:
         assert not disable_fwd_atomic_reduction and out_is_fp32
     if qk_starts is not None:
@@ -299,61 +161,17 @@ def _flex_flash_attn_forward(
             "deterministic + auto_range_merge lands in a later round"
         )
         assert not is_fp8, "fp8 + auto_range_merge lands in a later round"
-    if deterministic and q_ranges.shape[0] > 1:
-        # fixed merge order: one launch per q-disjoint slice group.
-        # NOTE: subset tensors must outlive the async kernel launches — hold
-        # references until the end of the loop (the ctypes kernel is invisible
-        # to torch's stream-aware allocator).
-        groups = _color_ranges(q_ranges.cpu().tolist())
-        keep = []
-        for g in groups:
-            idx = torch.tensor(g, dtype=torch.long, device=q.device)
-            sq = _subset(q_ranges, idx)
-            sk = _subset(k_ranges, idx)
-            st = _subset(attn_type_map, idx)
-            keep.append((sq, sk, st))
-            args.q_ranges = ptr(sq)
-            args.k_ranges = ptr(sk)
-            args.attn_type_map = ptr(st)
-            args.n_ranges = len(g)
-            check(fwd_fn(args), "magi_ffa_fwd[det]")
-        del keep
-    else:
-        check(fwd_fn(args), "magi_ffa_fwd")
+    _ffa_launch.fwd(
+        q, k, v, out, lse, q_ranges, k_ranges, attn_type_map,
+        locks=locks, max_logits=max_logits, qk_starts=qk_starts,
+        max_seqlen_q=max_seqlen_q, softmax_scale=softmax_scale,
+        softcap=softcap,
+        disable_fwd_atomic_reduction=disable_fwd_atomic_reduction,
+        sm_margin=sm_margin, deterministic=deterministic,
+    )
     if sink is not None:
         _apply_sink_postprocess(out, lse, sink, sink_layout, tq, hq, d)
     return out, AttnForwardMeta(lse=lse, max_logits=max_logits)
-
-
-def _check_sink(sink, sink_layout, tq, hq):
-    assert sink_layout in ("sh", "ssh"), f"unsupported sink_layout {sink_layout}"
-    sink = sink.contiguous().float()
-    if sink_layout == "sh":
-        assert sink.dim() == 2 and sink.shape[1] == hq, "sink must be [s_sink, hq]"
-        s_sink = sink.shape[0]
-    else:
-        assert sink.dim() == 3 and sink.shape[0] == tq and sink.shape[2] == hq, (
-            "sink must be [total_q, s_sink, hq]"
-        )
-        s_sink = sink.shape[1]
-    assert 1 <= s_sink <= 8, "seqlen_sink must be in [1, 8] (reference kMaxSeqlenSink)"
-    return sink, s_sink
-
-
-def _apply_sink_postprocess(out, lse, sink, sink_layout, tq, hq, d):
-    """Fold the sink logits into (out, lse) ONCE, after all slice merges
-    (reference flash_fwd_postprocess_kernel.h:39)."""
-    sink, s_sink = _check_sink(sink, sink_layout, tq, hq)
-    from .._ffa_lib import MagiSinkArgs
-
-    args = MagiSinkArgs(
-        out=ptr(out), lse=ptr(lse), sink=ptr(sink),
-        total_rows=tq, n_heads=hq, d=d, s_sink=s_sink,
-        ssh=int(sink_layout == "ssh"),
-        out_is_fp32=int(out.dtype == torch.float32),
-        stream=current_stream_ptr(),
-    )
-    check(_ffa_lib.lib().magi_ffa_sink_postprocess(args), "sink_postprocess")
 
 
 def _flex_flash_attn_forward_index(
@@ -385,8 +203,6 @@ def _flex_flash_attn_forward_index(
     max_logits (f32 [hq], preset to -inf by the caller) receives the per-head
     maximum scaled (softcapped) logit over valid slots and comes back in the
     meta; sink logits do not enter it."""
-    from .._ffa_lib import MagiFfaIndexArgs
-
     is_fp8 = q.dtype == torch.float8_e4m3fn
     assert q.dtype == torch.bfloat16 or is_fp8, "index_attn requires bf16 inputs"
     assert k.dtype == q.dtype and v.dtype == q.dtype, (
@@ -404,7 +220,6 @@ def _flex_flash_attn_forward_index(
     assert indices_2d.shape[0] == tq, (
         f"indices_2d rows ({indices_2d.shape[0]}) must match q token rows ({tq})"
     )
-    max_topk = indices_2d.shape[1]
     sink_f, s_sink = None, 0
     if sink is not None:
         sink_f, s_sink = _check_sink(sink, sink_layout, tq, hq)
@@ -417,21 +232,11 @@ def _flex_flash_attn_forward_index(
     out = torch.zeros(tq, hq, d, dtype=torch.bfloat16, device=q.device)
     lse = torch.full((tq, hq), float("-inf"), dtype=torch.float32, device=q.device)
 
-    args = MagiFfaIndexArgs(
-        q=ptr(q), k=ptr(k), v=ptr(v), out=ptr(out), lse=ptr(lse),
-        indices_2d=ptr(indices_2d),
-        total_q=tq, total_k=tk, max_topk=max_topk,
-        hq=hq, hk=hk, d=d,
-        softmax_scale=softmax_scale, softcap=softcap,
-        out_is_fp32=0, stream=current_stream_ptr(),
-        sink=ptr(sink_f), s_sink=s_sink,
-        sink_ssh=int(sink_layout == "ssh"), max_logits=ptr(max_logits),
+    _ffa_launch.fwd_index(
+        q, k, v, out, lse, indices_2d, softmax_scale, softcap,
+        sink_f=sink_f, s_sink=s_sink, sink_ssh=sink_layout == "ssh",
+        max_logits=max_logits,
     )
-    if is_fp8:
-        check(_ffa_lib.lib().magi_ffa_fwd_index_fp8(args),
-              "magi_ffa_fwd_index_fp8")
-    else:
-        check(_ffa_lib.lib().magi_ffa_fwd_index(args), "magi_ffa_fwd_index")
     return out, AttnForwardMeta(lse=lse, max_logits=max_logits)
 
 
@@ -478,66 +283,28 @@ def _flex_flash_attn_backward_index(
     already account for the sink (the dense path's argument); dsink (f32, the
     sink's shape) comes from magi_ffa_dsink over (sink, lse, dpsum). Without
     one dsink is None."""
-    from .._ffa_lib import MagiFfaIndexBwdArgs
-
     assert q.dtype == torch.bfloat16, "index_attn requires bf16 inputs"
     dout, q, k, v, out, lse, indices_2d = [
         maybe_contiguous(x) for x in (dout, q, k, v, out, lse, indices_2d)
     ]
-    if dout.dtype != q.dtype:
-        dout = dout.to(q.dtype)
-    tq, hq, d = q.shape
-    tk, hk, _ = k.shape
-    max_topk = indices_2d.shape[1]
-
+    dout = dout.to(q.dtype)
     dq = torch.zeros_like(q)
     dk = torch.zeros_like(k, dtype=torch.float32)
     dv = torch.zeros_like(v, dtype=torch.float32)
-    dpsum = torch.empty(tq, hq, dtype=torch.float32, device=q.device)
-
-    lib = _ffa_lib.lib()
-    pre = MagiFfaBwdArgs(
-        dout=ptr(dout), out=ptr(out), dpsum=ptr(dpsum),
-        total_q=tq, hq=hq, d=d,
-        out_is_fp32=int(out.dtype == torch.float32),
-        stream=current_stream_ptr(),
+    dsink = _ffa_launch.bwd_index(
+        dout, q, k, v, out, lse, indices_2d, dq, dk, dv,
+        softmax_scale, softcap, sink=sink, sink_layout=sink_layout,
     )
-    check(lib.magi_ffa_bwd_preprocess(pre), "magi_ffa_bwd_preprocess")
-    args = MagiFfaIndexBwdArgs(
-        dout=ptr(dout), q=ptr(q), k=ptr(k), v=ptr(v), lse=ptr(lse),
-        dpsum=ptr(dpsum), indices_2d=ptr(indices_2d),
-        dq=ptr(dq), dk=ptr(dk), dv=ptr(dv),
-        total_q=tq, total_k=tk, max_topk=max_topk,
-        hq=hq, hk=hk, d=d,
-        softmax_scale=softmax_scale, softcap=softcap,
-        stream=current_stream_ptr(),
-    )
-    check(lib.magi_ffa_bwd_index(args), "magi_ffa_bwd_index")
-    dsink = None
-    if sink is not None:
-        from .._ffa_lib import MagiSinkArgs
-
-        sink_f, s_sink = _check_sink(sink, sink_layout, tq, hq)
-        dsink = torch.zeros_like(sink_f)
-        sargs = MagiSinkArgs(
-            lse=ptr(lse), sink=ptr(sink_f), dsink=ptr(dsink), dpsum=ptr(dpsum),
-            total_rows=tq, n_heads=hq, d=d, s_sink=s_sink,
-            ssh=int(sink_layout == "ssh"), stream=current_stream_ptr(),
-        )
-        check(lib.magi_ffa_dsink(sargs), "magi_ffa_dsink")
     return dq, dk, dv, dsink
 
 
 def _index_attn_forward(ctx, q, k, v, indices_2d, softmax_scale, softcap,
                         sink, sink_layout, return_max_logits):
     """forward shared by IndexAttnFunc and IndexAttnSinkFunc"""
-    is_fp8 = q.dtype == torch.float8_e4m3fn
     d = q.shape[-1]
-    pad = _index_head_dim_pad(d) if is_fp8 else 0
-    max_logits = None
-    if return_max_logits:
-        max_logits = torch.full((q.shape[1],), float("-inf"),
-                                dtype=torch.float32, device=q.device)
+    pad = _index_head_dim_pad(d) if q.dtype == torch.float8_e4m3fn else 0
+    max_logits = (_ffa_launch.new_max_logits(q.shape[1], q.device)
+                  if return_max_logits else None)
     out, meta = _flex_flash_attn_forward_index(
         _pad_head_dim(q, pad), _pad_head_dim(k, pad), _pad_head_dim(v, pad),
         indices_2d, softmax_scale, softcap,
@@ -549,10 +316,9 @@ def _index_attn_forward(ctx, q, k, v, indices_2d, softmax_scale, softcap,
     ctx.pad = pad
     ctx.sink_layout = sink_layout
     # one call: a second mark_non_differentiable would replace the first
-    if max_logits is not None:
-        ctx.mark_non_differentiable(meta.lse, max_logits)
-    else:
-        ctx.mark_non_differentiable(meta.lse)
+    ctx.mark_non_differentiable(
+        *(t for t in (meta.lse, max_logits) if t is not None)
+    )
     return (out[..., :d] if pad else out), meta.lse, max_logits
 
 
@@ -562,11 +328,11 @@ def _index_attn_backward(ctx, dout, need_sink):
     q, k, v, out, lse, indices_2d, sink = ctx.saved_tensors
     in_dtype = q.dtype
     d = q.shape[-1]
-    if in_dtype == torch.float8_e4m3fn:
-        pad = ctx.pad
-        q, k, v, dout = [
-            _pad_head_dim(t.to(torch.bfloat16), pad) for t in (q, k, v, dout)
-        ]
+    # ctx.pad is 0 unless the inputs are fp8
+    q, k, v, dout = [
+        _pad_head_dim(t, ctx.pad)
+        for t in _ffa_launch.upcast_fp8(q, k, v, dout)
+    ]
     need_sink = need_sink and sink is not None
     dq, dk, dv, dsink = _flex_flash_attn_backward_index(
         dout, q, k, v, out, lse, indices_2d,
@@ -582,6 +348,15 @@ def _index_attn_backward(ctx, dout, need_sink):
     )
 
 
+def _input_grads(func_cls, **grads) -> tuple:
+    """What func_cls.backward returns: one gradient per forward input, in the
+    signature's order - the ones given by input name, None for the rest."""
+    code = func_cls.forward.__code__
+    names = code.co_varnames[1:code.co_argcount]  # the inputs, ctx left out
+    assert set(grads) <= set(names), (func_cls.__name__, names)
+    return tuple(grads.get(n) for n in names)
+
+
 class IndexAttnFunc(torch.autograd.Function):
     """Differentiable index attention: forward = the gather kernel, backward =
     preprocess + the gather/scatter kernel. The index tensor and the scalar
@@ -589,7 +364,7 @@ class IndexAttnFunc(torch.autograd.Function):
 
     fp8-e4m3 inputs run the fp8 forward kernel; their backward runs the bf16
     kernels over upcast operands with the fp8 forward's out/lse, and the
-    gradients are cast back to fp8 (the policy of FlexFlashAttnFunc.backward).
+    gradients are cast back to fp8 (the policy of _ffa_launch.upcast_fp8).
     An odd fp8 head dim is zero-padded here, not by the caller: the forward
     pads the bytes and the backward pads the bf16 upcast.
 
@@ -606,7 +381,7 @@ class IndexAttnFunc(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, _dlse):
         dq, dk, dv, _ = _index_attn_backward(ctx, dout, False)
-        return dq, dk, dv, None, None, None
+        return _input_grads(IndexAttnFunc, q=dq, k=dk, v=dv)
 
 
 class IndexAttnSinkFunc(torch.autograd.Function):
@@ -631,7 +406,7 @@ class IndexAttnSinkFunc(torch.autograd.Function):
         dq, dk, dv, dsink = _index_attn_backward(
             ctx, dout, ctx.needs_input_grad[6]
         )
-        return dq, dk, dv, None, None, None, dsink, None, None
+        return _input_grads(IndexAttnSinkFunc, q=dq, k=dk, v=dv, sink=dsink)
 
 
 def _flex_flash_attn_backward(
@@ -662,12 +437,10 @@ def _flex_flash_attn_backward(
     auto_range_merge: bool = False,
     **_unused,
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
-    dout, q, k, v, out, q_ranges, k_ranges = [
-        maybe_contiguous(x) for x in (dout, q, k, v, out, q_ranges, k_ranges)
-    ]
-    attn_type_map = maybe_contiguous(attn_type_map)
-    tq, hq, d = q.shape
-    tk, hk, _ = k.shape
+    dout, q, k, v, out, q_ranges, k_ranges, attn_type_map = map(
+        maybe_contiguous, (dout, q, k, v, out, q_ranges, k_ranges, attn_type_map)
+    )
+    tq, hq, _ = q.shape
 
     # fp32 accumulators, atomically reduced by the kernel
     dq = torch.zeros_like(q, dtype=torch.float32) if dq is None else dq
@@ -679,57 +452,32 @@ def _flex_flash_attn_backward(
     if max_seqlen_k is None:
         max_seqlen_k = _max_seqlen_of(k_ranges)
 
-    args = MagiFfaBwdArgs(
-        dout=ptr(dout), q=ptr(q), k=ptr(k), v=ptr(v), out=ptr(out),
-        lse=ptr(lse), dq=ptr(dq), dk=ptr(dk), dv=ptr(dv), dpsum=ptr(dpsum),
-        q_ranges=ptr(q_ranges), k_ranges=ptr(k_ranges),
-        attn_type_map=ptr(attn_type_map),
-        n_ranges=q_ranges.shape[0], total_q=tq, total_k=tk,
-        hq=hq, hk=hk, d=d, max_seqlen_k=max_seqlen_k,
-        out_is_fp32=int(out.dtype == torch.float32),
-        softmax_scale=softmax_scale, softcap=softcap,
-        cu_margin=sm_margin, stream=current_stream_ptr(),
+    args = _ffa_launch.bwd_args(
+        dout, out, dpsum, q=q, k=k, v=v, lse=lse, dq=dq, dk=dk, dv=dv,
+        q_ranges=q_ranges, k_ranges=k_ranges, attn_type_map=attn_type_map,
+        max_seqlen_k=max_seqlen_k, softmax_scale=softmax_scale,
+        softcap=softcap, sm_margin=sm_margin,
     )
-    lib = _ffa_lib.lib()
-    check(lib.magi_ffa_bwd_preprocess(args), "magi_ffa_bwd_preprocess")
+    _ffa_launch.bwd_preprocess(args)
     if sink is not None:
-        # dsink needs only (sink, lse, dpsum); the q/k/v gradients pick the
-        # sink up automatically through the corrected lse saved by forward
         sink_f, s_sink = _check_sink(sink, sink_layout, tq, hq)
-        if dsink is None:
-            dsink = torch.zeros_like(sink_f)
-        from .._ffa_lib import MagiSinkArgs
-
-        sargs = MagiSinkArgs(
-            lse=ptr(lse), sink=ptr(sink_f), dsink=ptr(dsink), dpsum=ptr(dpsum),
-            total_rows=tq, n_heads=hq, d=d, s_sink=s_sink,
-            ssh=int(sink_layout == "ssh"), stream=current_stream_ptr(),
+        dsink = _ffa_launch.bwd_dsink(
+            sink_f, s_sink, sink_layout == "ssh", lse, dpsum, dsink
         )
-        check(lib.magi_ffa_dsink(sargs), "magi_ffa_dsink")
+    merged = None
     if deterministic:
         assert not auto_range_merge, (
             "deterministic + auto_range_merge lands in a later round"
         )
-        run_bwd_deterministic(args, q_ranges, k_ranges, attn_type_map,
-                              hq, hk, q.device)
     elif auto_range_merge:
         # dq pass: unique q ranges with k segments; dkv pass: unique k
         # ranges with q segments (reference bwd_kq_map)
-        mq, _, sk_i, sq_t, inv_q, _ = merge_ranges(
-            q_ranges, k_ranges, attn_type_map
-        )
-        qk_starts = _seg_starts(inv_q, q_ranges.shape[0])
-        mk, _, sq_i, sk_t, inv_k, _ = merge_ranges(
-            k_ranges, q_ranges, attn_type_map
-        )
-        kq_starts = _seg_starts(inv_k, k_ranges.shape[0])
-        run_bwd_passes(
-            args, q.device,
-            dq_tables=(mq, sk_i, sq_t, qk_starts),
-            dkv_tables=(mk, sq_i, sk_t, kq_starts),
-        )
-    else:
-        run_bwd_passes(args, q.device)
+        merged = (_merged_tables(q_ranges, k_ranges, attn_type_map),
+                  _merged_tables(k_ranges, q_ranges, attn_type_map))
+    _ffa_launch.run_bwd(
+        args, q_ranges, k_ranges, attn_type_map, q.device,
+        deterministic=deterministic, merged=merged,
+    )
     return dq, dk, dv, dsink
 
 
@@ -759,16 +507,13 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             assert attn_type_map is not None, (
                 "auto_range_merge requires an explicit attn_type_map"
             )
-            mq, _, sk_i, st, inv_q, _ = merge_ranges(
-                q_ranges, k_ranges, attn_type_map
+            fwd_q_ranges, fwd_k_ranges, fwd_tm, fwd_qk_starts = (
+                _merged_tables(q_ranges, k_ranges, attn_type_map)
             )
-            fwd_q_ranges, fwd_k_ranges, fwd_tm = mq, sk_i, st
-            fwd_qk_starts = _seg_starts(inv_q, q_ranges.shape[0])
         max_logits = None
         if return_max_logits:
             assert q.shape[1] <= 128, "num_qheads must be <= 128 (reference cap)"
-            max_logits = torch.full((q.shape[1],), float("-inf"),
-                                    dtype=torch.float32, device=q.device)
+            max_logits = _ffa_launch.new_max_logits(q.shape[1], q.device)
 
         out, meta = _flex_flash_attn_forward(
             q=q, k=k, v=v, sink=sink, sink_layout=sink_layout,
@@ -782,10 +527,8 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             qk_starts=fwd_qk_starts,
         )
         lse = meta.lse
-        if q.dtype == torch.float8_e4m3fn:
-            out = out.to(torch.bfloat16)  # fp8 extension returns bf16 out
-        elif out.dtype != q.dtype:
-            out = out.to(q.dtype)
+        # fp8 extension returns bf16 out
+        out = out.to(torch.bfloat16 if q.dtype == torch.float8_e4m3fn else q.dtype)
         ctx.save_for_backward(q, k, v, out, lse, q_ranges, k_ranges,
                               attn_type_map, sink)
         ctx.softmax_scale = softmax_scale
@@ -805,16 +548,7 @@ class FlexFlashAttnFunc(torch.autograd.Function):
         (q, k, v, out, lse, q_ranges, k_ranges, attn_type_map,
          sink) = ctx.saved_tensors
         in_dtype = q.dtype
-        if in_dtype == torch.float8_e4m3fn:
-            # fp8 backward runs on the bf16 kernels over upcast operands
-            # (standard mixed-precision practice; fp8 MFMA backward is a
-            # later-round item). Gradients are produced in bf16 precision and
-            # cast to the input dtype at return, as autograd requires.
-            q = q.to(torch.bfloat16)
-            k = k.to(torch.bfloat16)
-            v = v.to(torch.bfloat16)
-            out = out.to(torch.bfloat16) if out.dtype == torch.float8_e4m3fn else out
-            dout = dout.to(torch.bfloat16)
+        q, k, v, out, dout = _ffa_launch.upcast_fp8(q, k, v, out, dout)
         dq, dk, dv, dsink = _flex_flash_attn_backward(
             dout=dout, q=q, k=k, v=v, sink=sink, sink_layout=ctx.sink_layout,
             out=out, lse=lse, dq=None, dk=None, dv=None, dsink=None,
@@ -826,12 +560,12 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             max_seqlen_k=ctx.max_seqlen_k,
             auto_range_merge=ctx.auto_range_merge,
         )
-        dq = dq.to(in_dtype)
-        dk = dk.to(in_dtype)
-        dv = dv.to(in_dtype)
         if sink is not None and dsink is not None:
             dsink = dsink.to(sink.dtype)
-        return (dq, dk, dv, dsink) + (None,) * 24
+        return _input_grads(
+            FlexFlashAttnFunc, q=dq.to(in_dtype), k=dk.to(in_dtype),
+            v=dv.to(in_dtype), sink=dsink,
+        )
 
 
 def flex_flash_attn_func(
@@ -943,10 +677,8 @@ def flex_flash_attn_func(
                     sink, sink_layout, return_max_logits,
                 )
                 return out_, AttnForwardMeta(lse=lse_, max_logits=ml_)
-            ml_ = None
-            if return_max_logits:
-                ml_ = torch.full((q_.shape[1],), float("-inf"),
-                                 dtype=torch.float32, device=q_.device)
+            ml_ = (_ffa_launch.new_max_logits(q_.shape[1], q_.device)
+                   if return_max_logits else None)
             return _flex_flash_attn_forward_index(
                 q_, k_, v_, indices_2d, softmax_scale, softcap,
                 sink=sink, sink_layout=sink_layout, max_logits=ml_,
