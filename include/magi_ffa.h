@@ -7,7 +7,10 @@
  * in THIS repo) binds them via ctypes; INTEGRATION.md shows the binding a
  * maintainer would add.
  *
- * Conventions: all device pointers; q/k/v bf16 row-major [tokens, heads, dim];
+ * Conventions: all device pointers; q/k/v row-major [tokens, heads, dim], bf16
+ * unless an entry says otherwise: the dense entries (magi_ffa_fwd,
+ * magi_ffa_bwd*) take bf16 or fp16 by the elem_type member of their args,
+ * the *_fp8 entries raw e4m3 bytes; the index entries are bf16 only;
  * ranges int32 [n,2] half-open; attn_type_map int32 (0=full, 1=causal,
  * 2=inv_causal, 3=bi_causal; semantics = reference flex_flash_attn.py:1247-1341);
  * stream is a hipStream_t. All functions return 0 on success, nonzero hipError_t
@@ -22,11 +25,16 @@
 extern "C" {
 #endif
 
+/* Element type of the dense entries' 16-bit tensors (elem_type members). */
+#define MAGI_FFA_ELEM_BF16 0
+#define MAGI_FFA_ELEM_FP16 1
+
 typedef struct magi_ffa_fwd_args {
-  const void* q;            /* bf16 [total_q, hq, d] */
-  const void* k;            /* bf16 [total_k, hk, d] */
-  const void* v;            /* bf16 [total_k, hk, d] */
-  void* out;                /* f32 (accumulate/merge mode) or bf16 [total_q, hq, d] */
+  const void* q;            /* elem_type [total_q, hq, d] */
+  const void* k;            /* elem_type [total_k, hk, d] */
+  const void* v;            /* elem_type [total_k, hk, d] */
+  void* out;                /* f32 (accumulate/merge mode) or elem_type
+                               [total_q, hq, d] */
   float* lse;               /* f32 [total_q, hq], caller-initialised to -inf */
   const int32_t* q_ranges;  /* [n, 2] */
   const int32_t* k_ranges;  /* [n, 2] */
@@ -51,20 +59,28 @@ typedef struct magi_ffa_fwd_args {
                                softmax scale becomes softcap (reference
                                mainloop_fwd...hpp:466-489) */
   int32_t out_is_fp32;      /* 1: out is f32 accumulator (merge into it);
-                               0: bf16 direct store (requires disable_atomic_reduction) */
+                               0: elem_type direct store (requires
+                               disable_atomic_reduction) */
   int32_t disable_atomic_reduction; /* 1: q_ranges disjoint, skip lock/merge */
   int32_t cu_margin;        /* CUs left free for comm kernels (sm_margin analogue) */
   void* stream;             /* hipStream_t */
+  int32_t elem_type;        /* MAGI_FFA_ELEM_*: type of q/k/v, and of out when
+                               out_is_fp32 == 0; a zero-filled struct is bf16 */
 } magi_ffa_fwd_args;
 
+/* Validation of magi_ffa_fwd, in this order, all before any HIP call: -1 null
+ * pointer, -2 d not in {64, 128, 192}, -3 hq % hk != 0, -9 elem_type not one
+ * of MAGI_FFA_ELEM_*; then n_ranges <= 0 returns 0 without a launch; -4 merge
+ * mode without locks, -5 more than 65535 ranges, -10 merge mode into a 16-bit
+ * out. magi_ffa_fwd_fp8 (raw e4m3 q/k/v) ignores elem_type. */
 int magi_ffa_fwd(const magi_ffa_fwd_args* args);
 
 typedef struct magi_ffa_bwd_args {
-  const void* dout;         /* bf16 [total_q, hq, d] */
-  const void* q;            /* bf16 [total_q, hq, d] */
-  const void* k;            /* bf16 [total_k, hk, d] */
-  const void* v;            /* bf16 [total_k, hk, d] */
-  const void* out;          /* bf16 or f32 [total_q, hq, d] (forward output) */
+  const void* dout;         /* elem_type [total_q, hq, d] */
+  const void* q;            /* elem_type [total_q, hq, d] */
+  const void* k;            /* elem_type [total_k, hk, d] */
+  const void* v;            /* elem_type [total_k, hk, d] */
+  const void* out;          /* elem_type or f32 [total_q, hq, d] (forward output) */
   const float* lse;         /* f32 [total_q, hq] */
   float* dq;                /* f32 [total_q, hq, d], zeroed, atomic-accumulated */
   float* dk;                /* f32 [total_k, hk, d], zeroed, atomic-accumulated */
@@ -88,7 +104,14 @@ typedef struct magi_ffa_bwd_args {
   float softcap;
   int32_t cu_margin;
   void* stream;
+  int32_t elem_type;        /* MAGI_FFA_ELEM_*: type of dout/q/k/v, and of out
+                               when out_is_fp32 == 0; zero-filled = bf16 */
 } magi_ffa_bwd_args;
+
+/* Every backward entry below (_preprocess, _dq, _dkv, _dv, _dk and
+ * magi_ffa_bwd) returns -9 for an elem_type that is not one of
+ * MAGI_FFA_ELEM_*, after its null-pointer (-1), head-dim (-2) and GQA (-3)
+ * checks and before any HIP call. dq/dk/dv stay f32 for both element types. */
 
 /* dPsum preprocess: dpsum[t,h] = sum_d dout[t,h,d] * out[t,h,d]
  * (reference flash_bwd_preprocess_kernel.h:42). */
@@ -311,6 +334,14 @@ int magi_ffa_bwd_index(const magi_ffa_index_bwd_args* args);
 
 /* Version/identity probe so tests can verify the native library is loaded. */
 int magi_ffa_abi_version(void);
+
+/* sizeof of a public args struct as the library was compiled, for a binding
+ * to check its own mirror against before it passes one in (a mismatch would
+ * make a kernel read garbage pointers). which: 0 magi_ffa_fwd_args,
+ * 1 magi_ffa_bwd_args, 2 magi_range_op_args, 3 magi_sink_args,
+ * 4 magi_correct_args, 5 magi_ffa_index_args, 6 magi_ffa_index_bwd_args;
+ * anything else returns -1. */
+int magi_ffa_args_size(int which);
 
 #ifdef __cplusplus
 } /* extern "C" */

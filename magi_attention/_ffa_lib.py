@@ -18,6 +18,15 @@ _lib: ctypes.CDLL | None = None
 _load_error: Exception | None = None
 
 
+# elem_type of MagiFfaFwdArgs / MagiFfaBwdArgs (MAGI_FFA_ELEM_* in magi_ffa.h)
+ELEM_BF16, ELEM_FP16 = 0, 1
+
+
+def elem_type_of(dtype: torch.dtype) -> int:
+    """elem_type of a dense launch whose q is of dtype (fp8 entries ignore it)"""
+    return ELEM_FP16 if dtype == torch.float16 else ELEM_BF16
+
+
 class MagiFfaFwdArgs(ctypes.Structure):
     _fields_ = [
         ("q", ctypes.c_void_p),
@@ -44,6 +53,7 @@ class MagiFfaFwdArgs(ctypes.Structure):
         ("disable_atomic_reduction", ctypes.c_int32),
         ("cu_margin", ctypes.c_int32),
         ("stream", ctypes.c_void_p),
+        ("elem_type", ctypes.c_int32),  # ELEM_BF16 (default) or ELEM_FP16
     ]
 
 
@@ -75,6 +85,7 @@ class MagiFfaBwdArgs(ctypes.Structure):
         ("softcap", ctypes.c_float),
         ("cu_margin", ctypes.c_int32),
         ("stream", ctypes.c_void_p),
+        ("elem_type", ctypes.c_int32),  # ELEM_BF16 (default) or ELEM_FP16
     ]
 
 
@@ -261,6 +272,8 @@ def _try_load() -> ctypes.CDLL | None:
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
         lib.magi_ffa_abi_version.restype = ctypes.c_int
+        lib.magi_ffa_args_size.argtypes = [ctypes.c_int]
+        lib.magi_ffa_args_size.restype = ctypes.c_int
         _lib = lib
     except OSError as e:  # missing .so or missing HIP runtime
         _load_error = e

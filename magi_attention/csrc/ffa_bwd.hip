@@ -53,11 +53,14 @@
 
 DEV_INLINE bool wave_alive(int m0, int qe) { return m0 < qe; }
 
+// ET: element type of dout/q/k/v and of a 16-bit out, bf16_t or f16_t
+// (ElemTraits, ffa_device.h); P and dS are rounded to ET before their MFMAs
+template <class ET>
 struct BwdParams {
-  const bf16_t* dout;
-  const bf16_t* q;
-  const bf16_t* k;
-  const bf16_t* v;
+  const ET* dout;
+  const ET* q;
+  const ET* k;
+  const ET* v;
   const void* out;
   const float* lse;
   float* dq;
@@ -82,23 +85,25 @@ struct BwdParams {
 };
 
 // ---------------- preprocess: dpsum = rowsum(dO * O) ----------------
-template <bool OUT_F32>
-__global__ __launch_bounds__(256) void bwd_preprocess_kernel(BwdParams p, int d,
+template <class ET, bool OUT_F32>
+__global__ __launch_bounds__(256) void bwd_preprocess_kernel(BwdParams<ET> p,
+                                                             int d,
                                                              long long n_rows) {
+  using Tr = ElemTraits<ET>;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n_rows) return;
   const int lane = threadIdx.x & 63;
   const int per = d / 64;
-  const bf16_t* do_p = p.dout + row * d;
+  const ET* do_p = p.dout + row * d;
   float acc = 0.f;
   for (int e = 0; e < per; ++e) {
     const int idx = lane * per + e;
-    const float dov = (float)do_p[idx];
+    const float dov = Tr::to_f32(do_p[idx]);
     float ov;
     if (OUT_F32)
       ov = ((const float*)p.out)[row * d + idx];
     else
-      ov = (float)((const bf16_t*)p.out)[row * d + idx];
+      ov = Tr::to_f32(((const ET*)p.out)[row * d + idx]);
     acc += dov * ov;
   }
 #pragma unroll
@@ -124,9 +129,11 @@ __global__ __launch_bounds__(256) void bwd_preprocess_kernel(BwdParams p, int d,
 // 8-wave kernels run the 3-ring; the fused mode keeps 2 (its K/V tiles + a
 // 3-ring exceed the 160 KB LDS), and so do 4-wave workgroups (3 buffers
 // exceed the 80 KB/WG budget of 2 blocks/CU).
-template <int D, bool HAS_SOFTCAP, int MODE, int WAVES>
+template <class ET, int D, bool HAS_SOFTCAP, int MODE, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1)
-void ffa_bwd_dkv_kernel(BwdParams p) {
+void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
+  using Tr = ElemTraits<ET>;
+  using vec8 = typename Tr::x8;
   static_assert(WAVES == 4 || (WAVES == 8 && D != 192), "unsupported shape");
   constexpr int NBUF = (MODE != 0 && WAVES == 8) ? 3 : 2;
   constexpr bool WANT_DV = MODE != 2;
@@ -231,11 +238,11 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
                 "LDS budget");
   __shared__ __attribute__((aligned(16))) char smem[
       NBUF * 2 * QITER * ROWB + LSELDS + KVLDS];
-  auto lds_q = [&](int buf) -> __bf16* {
-    return (__bf16*)(smem + (2 * buf) * QITER * ROWB);
+  auto lds_q = [&](int buf) -> ET* {
+    return (ET*)(smem + (2 * buf) * QITER * ROWB);
   };
-  auto lds_do = [&](int buf) -> __bf16* {
-    return (__bf16*)(smem + (2 * buf + 1) * QITER * ROWB);
+  auto lds_do = [&](int buf) -> ET* {
+    return (ET*)(smem + (2 * buf + 1) * QITER * ROWB);
   };
   // lse / dpsum, staged by LDS-DMA (one dword per lane: lanes 0-31 lse,
   // 32-63 dpsum), one call per 32-row group: layout per buffer is
@@ -245,9 +252,9 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   };
   // MODE 0: per-wave K and V tiles (BWD_BN rows x D, same 32-B XOR swizzle
   // as the Q/dO images so the A-fragment reads reuse the qf addressing)
-  __bf16* lds_kt = (__bf16*)(smem + NBUF * 2 * QITER * ROWB + LSELDS) +
+  ET* lds_kt = (ET*)(smem + NBUF * 2 * QITER * ROWB + LSELDS) +
                    wave * BWD_BN * ROWE;
-  __bf16* lds_vt = (__bf16*)(smem + NBUF * 2 * QITER * ROWB + LSELDS +
+  ET* lds_vt = (ET*)(smem + NBUF * 2 * QITER * ROWB + LSELDS +
                              KVLDS / 2) +
                    wave * BWD_BN * ROWE;
 
@@ -261,15 +268,15 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   // from global memory in the loop either: each subtile takes its K (and V)
   // fragments off the wave's LDS tile staged below, so the registers are
   // subtile-local. kp_row serves the split modes only.
-  const bf16_t* kp_row = p.k + (size_t)kcl * k_pitch + (size_t)kh * D + hi * 8;
-  bf16x8 kfA[V_IN_LDS ? 1 : DF], vfA[(WANT_DK && !V_IN_LDS) ? DF : 1];
+  const ET* kp_row = p.k + (size_t)kcl * k_pitch + (size_t)kh * D + hi * 8;
+  vec8 kfA[V_IN_LDS ? 1 : DF], vfA[(WANT_DK && !V_IN_LDS) ? DF : 1];
   if constexpr (!V_IN_LDS) {
-    const bf16_t* vp = p.v + (size_t)kcl * k_pitch + (size_t)kh * D;
+    const ET* vp = p.v + (size_t)kcl * k_pitch + (size_t)kh * D;
 #pragma unroll
     for (int dd = 0; dd < DF; ++dd) {
-      kfA[dd] = *(const bf16x8*)(kp_row - hi * 8 + dd * 16 + hi * 8);
+      kfA[dd] = *(const vec8*)(kp_row - hi * 8 + dd * 16 + hi * 8);
       if constexpr (WANT_DK)
-        vfA[dd] = *(const bf16x8*)(vp + dd * 16 + hi * 8);
+        vfA[dd] = *(const vec8*)(vp + dd * 16 + hi * 8);
     }
   }
   constexpr int ROWS_PER_GLDS_V = 1024 / ROWB;
@@ -326,8 +333,8 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
   constexpr int GLDS_PER_WAVE =
       (GLDS_TOTAL % WAVES == 0) ? GLDS_TOTAL / WAVES : 0;  // 0 = non-uniform
   // block-uniform operands of the staging addresses (scalar registers)
-  const bf16_t* q_head = p.q + (size_t)h * D;
-  const bf16_t* do_head = p.dout + (size_t)h * D;
+  const ET* q_head = p.q + (size_t)h * D;
+  const ET* do_head = p.dout + (size_t)h * D;
   const int smem_byte = (int)(unsigned long long)(
       (__attribute__((address_space(3))) const char*)smem);
   auto stage_glds = [&](int buf, int m0x) {
@@ -453,8 +460,8 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
     for (int sub = 0; sub < NSUB; ++sub) {
     const int ms = m0 + sub * BWD_BM;
     if (ms >= q_hi) break;  // q_hi is block-uniform
-    const __bf16* lqb = lds_q(cur) + sub * BWD_BM * ROWE;
-    const __bf16* ldb = lds_do(cur) + sub * BWD_BM * ROWE;
+    const ET* lqb = lds_q(cur) + sub * BWD_BM * ROWE;
+    const ET* ldb = lds_do(cur) + sub * BWD_BM * ROWE;
     const float* lse_t = nullptr;
     const float* dps_t = nullptr;
     // MODE0: row (lane & 31) of this subtile (bpermute)
@@ -489,22 +496,22 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
 #pragma unroll
         for (int dd = 0; dd < DF; ++dd) {
           const int off = swz(lo32, lo32 * ROWB + dd * 32 + hi * 16);
-          bf16x8 dof = *(const bf16x8*)((const char*)ldb + off);
-          bf16x8 vf = *(const bf16x8*)(vt_c + off);
-          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, vf, dp, 0, 0, 0);
-          bf16x8 qf = *(const bf16x8*)((const char*)lqb + off);
-          bf16x8 kf = *(const bf16x8*)(kt_c + off);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kf, s, 0, 0, 0);
+          vec8 dof = *(const vec8*)((const char*)ldb + off);
+          vec8 vf = *(const vec8*)(vt_c + off);
+          dp = Tr::mfma(dof, vf, dp);
+          vec8 qf = *(const vec8*)((const char*)lqb + off);
+          vec8 kf = *(const vec8*)(kt_c + off);
+          s = Tr::mfma(qf, kf, s);
         }
       } else {
 #pragma unroll
       for (int dd = 0; dd < DF; ++dd) {
         const int off = swz(lo32, lo32 * ROWB + dd * 32 + hi * 16);
-        bf16x8 qf = *(const bf16x8*)((const char*)lqb + off);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kfA[dd], s, 0, 0, 0);
+        vec8 qf = *(const vec8*)((const char*)lqb + off);
+        s = Tr::mfma(qf, kfA[dd], s);
         if constexpr (WANT_DK) {
-          bf16x8 dof = *(const bf16x8*)((const char*)ldb + off);
-          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof, vfA[dd], dp, 0, 0, 0);
+          vec8 dof = *(const vec8*)((const char*)ldb + off);
+          dp = Tr::mfma(dof, vfA[dd], dp);
         }
       }
       }
@@ -594,31 +601,30 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
         const int rb3 = (row1 + 16) * ROWB + lane8;
         // software-pipelined B-frag matmul: step j+1's fragment reads issue
         // under step j's MFMA (see dq kernel note)
-        auto pipe_mm = [&](int tbase, bf16x8 a0, bf16x8 a1, f32x16* acc) {
-          bf16x8 bcur = tr16_frag(tbase + rb0 + ((16 * qhalf * 2) ^ sw0),
+        auto pipe_mm = [&](int tbase, vec8 a0, vec8 a1, f32x16* acc) {
+          vec8 bcur = Tr::tr16(tbase + rb0 + ((16 * qhalf * 2) ^ sw0),
                                   tbase + rb1 + ((16 * qhalf * 2) ^ sw1));
 #pragma unroll
           for (int j = 0; j < 2 * DT; ++j) {
-            bf16x8 bnext = bcur;
+            vec8 bnext = bcur;
             if (j + 1 < 2 * DT) {
               const int dcoln = (((j + 1) >> 1) * 32 + 16 * qhalf) * 2;
               if ((j + 1) & 1)
-                bnext = tr16_frag(tbase + rb2 + (dcoln ^ sw2),
+                bnext = Tr::tr16(tbase + rb2 + (dcoln ^ sw2),
                                   tbase + rb3 + (dcoln ^ sw3));
               else
-                bnext = tr16_frag(tbase + rb0 + (dcoln ^ sw0),
+                bnext = Tr::tr16(tbase + rb0 + (dcoln ^ sw0),
                                   tbase + rb1 + (dcoln ^ sw1));
             }
-            acc[j >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                (j & 1) ? a1 : a0, bcur, acc[j >> 1], 0, 0, 0);
+            acc[j >> 1] = Tr::mfma((j & 1) ? a1 : a0, bcur, acc[j >> 1]);
             bcur = bnext;
           }
         };
         if constexpr (MODE == 1) {
-          pipe_mm(do_base, cframe_to_afrag(pv, 0), cframe_to_afrag(pv, 1),
+          pipe_mm(do_base, Tr::afrag(pv, 0), Tr::afrag(pv, 1),
                   acc_dv);
         } else if constexpr (MODE == 2) {
-          pipe_mm(q_base, cframe_to_afrag(dsv, 0), cframe_to_afrag(dsv, 1),
+          pipe_mm(q_base, Tr::afrag(dsv, 0), Tr::afrag(dsv, 1),
                   acc_dk);
         } else {
           // MODE 0 (fused dK+dV): INTERLEAVE the two independent MFMA
@@ -626,29 +632,25 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
           // OTHER stream's in-flight MFMA, which a single serialized stream
           // cannot do (the allocator coalesces any explicit double-buffer
           // at this register pressure).
-          bf16x8 pa0 = cframe_to_afrag(pv, 0);
-          bf16x8 pa1 = cframe_to_afrag(pv, 1);
-          bf16x8 da0 = cframe_to_afrag(dsv, 0);
-          bf16x8 da1 = cframe_to_afrag(dsv, 1);
+          vec8 pa0 = Tr::afrag(pv, 0);
+          vec8 pa1 = Tr::afrag(pv, 1);
+          vec8 da0 = Tr::afrag(dsv, 0);
+          vec8 da1 = Tr::afrag(dsv, 1);
 #pragma unroll
           for (int dt = 0; dt < DT; ++dt) {
             const int dcol = (dt * 32 + 16 * qhalf) * 2;
-            bf16x8 bdo = tr16_frag(do_base + rb0 + (dcol ^ sw0),
+            vec8 bdo = Tr::tr16(do_base + rb0 + (dcol ^ sw0),
                                    do_base + rb1 + (dcol ^ sw1));
-            acc_dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                pa0, bdo, acc_dv[dt], 0, 0, 0);
-            bf16x8 bq = tr16_frag(q_base + rb0 + (dcol ^ sw0),
+            acc_dv[dt] = Tr::mfma(pa0, bdo, acc_dv[dt]);
+            vec8 bq = Tr::tr16(q_base + rb0 + (dcol ^ sw0),
                                   q_base + rb1 + (dcol ^ sw1));
-            acc_dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                da0, bq, acc_dk[dt], 0, 0, 0);
-            bf16x8 bdo1 = tr16_frag(do_base + rb2 + (dcol ^ sw2),
+            acc_dk[dt] = Tr::mfma(da0, bq, acc_dk[dt]);
+            vec8 bdo1 = Tr::tr16(do_base + rb2 + (dcol ^ sw2),
                                     do_base + rb3 + (dcol ^ sw3));
-            acc_dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                pa1, bdo1, acc_dv[dt], 0, 0, 0);
-            bf16x8 bq1 = tr16_frag(q_base + rb2 + (dcol ^ sw2),
+            acc_dv[dt] = Tr::mfma(pa1, bdo1, acc_dv[dt]);
+            vec8 bq1 = Tr::tr16(q_base + rb2 + (dcol ^ sw2),
                                    q_base + rb3 + (dcol ^ sw3));
-            acc_dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                da1, bq1, acc_dk[dt], 0, 0, 0);
+            acc_dk[dt] = Tr::mfma(da1, bq1, acc_dk[dt]);
           }
         }
       }
@@ -696,9 +698,11 @@ void ffa_bwd_dkv_kernel(BwdParams p) {
 // D=192 builds spill at 8 waves' 256-register cap and exist at 4 only).
 // 8 waves run the 3-slot staging ring (see the dkv kernel note); 4 waves keep
 // 2 slots (3 buffers exceed the 80 KB/WG budget of 2 blocks/CU).
-template <int D, bool HAS_SOFTCAP, int WAVES>
+template <class ET, int D, bool HAS_SOFTCAP, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2)
-void ffa_bwd_dq_kernel(BwdParams p) {
+void ffa_bwd_dq_kernel(BwdParams<ET> p) {
+  using Tr = ElemTraits<ET>;
+  using vec8 = typename Tr::x8;
   static_assert(WAVES == 4 || (WAVES == 8 && D != 192), "unsupported shape");
   constexpr int NBUF = WAVES == 8 ? 3 : 2;
   constexpr int DF = D / 16;
@@ -771,22 +775,22 @@ void ffa_bwd_dq_kernel(BwdParams p) {
   constexpr int KITER = 2 * BWD_BN;
   static_assert(NBUF * 2 * KITER * ROWB <= 163840, "LDS budget");
   __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * KITER * ROWB];
-  auto lds_k = [&](int buf) -> __bf16* {
-    return (__bf16*)(smem + (2 * buf) * KITER * ROWB);
+  auto lds_k = [&](int buf) -> ET* {
+    return (ET*)(smem + (2 * buf) * KITER * ROWB);
   };
-  auto lds_v = [&](int buf) -> __bf16* {
-    return (__bf16*)(smem + (2 * buf + 1) * KITER * ROWB);
+  auto lds_v = [&](int buf) -> ET* {
+    return (ET*)(smem + (2 * buf + 1) * KITER * ROWB);
   };
 
   // persistent per-wave operands: Q and dO fragments (B-layout rows)
-  bf16x8 qf[DF], dof[DF];
+  vec8 qf[DF], dof[DF];
   {
-    const bf16_t* qp = p.q + (size_t)qcl * q_pitch + (size_t)h * D;
-    const bf16_t* dp = p.dout + (size_t)qcl * q_pitch + (size_t)h * D;
+    const ET* qp = p.q + (size_t)qcl * q_pitch + (size_t)h * D;
+    const ET* dp = p.dout + (size_t)qcl * q_pitch + (size_t)h * D;
 #pragma unroll
     for (int dd = 0; dd < DF; ++dd) {
-      qf[dd] = *(const bf16x8*)(qp + dd * 16 + hi * 8);
-      dof[dd] = *(const bf16x8*)(dp + dd * 16 + hi * 8);
+      qf[dd] = *(const vec8*)(qp + dd * 16 + hi * 8);
+      dof[dd] = *(const vec8*)(dp + dd * 16 + hi * 8);
     }
   }
   float lse_q = qvalid ? p.lse[(size_t)qrow * p.hq + h] : INFINITY;
@@ -877,8 +881,8 @@ void ffa_bwd_dq_kernel(BwdParams p) {
     for (int sub = 0; sub < 2; ++sub) {
     const int ns = n0 + sub * BWD_BN;
     if (ns >= k_hi) break;  // k_hi is block-uniform
-    const __bf16* lkb = lds_k(cur) + sub * BWD_BN * ROWE;
-    const __bf16* lvb = lds_v(cur) + sub * BWD_BN * ROWE;
+    const ET* lkb = lds_k(cur) + sub * BWD_BN * ROWE;
+    const ET* lvb = lds_v(cur) + sub * BWD_BN * ROWE;
 
     if (wave_alive(m0, qe) && ns + BWD_BN > wk_lo && ns < wk_hi) {
       // ---- S^T = K Q^T ; dP^T = V dO^T (K/V A-frags from LDS rows) ----
@@ -888,21 +892,21 @@ void ffa_bwd_dq_kernel(BwdParams p) {
       f32x16 sA = (f32x16)(0.f), dpA = (f32x16)(0.f);
       {
         const int off0 = swz(lo32, lo32 * ROWB + hi * 16);
-        bf16x8 kf = *(const bf16x8*)((const char*)lkb + off0);
-        bf16x8 vf = *(const bf16x8*)((const char*)lvb + off0);
+        vec8 kf = *(const vec8*)((const char*)lkb + off0);
+        vec8 vf = *(const vec8*)((const char*)lvb + off0);
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read x2
 #pragma unroll
         for (int dd = 0; dd < DF; ++dd) {
-          bf16x8 kn = kf, vn = vf;
+          vec8 kn = kf, vn = vf;
           if (dd + 1 < DF) {
             const int off = swz(lo32, lo32 * ROWB + (dd + 1) * 32 + hi * 16);
-            kn = *(const bf16x8*)((const char*)lkb + off);
-            vn = *(const bf16x8*)((const char*)lvb + off);
+            kn = *(const vec8*)((const char*)lkb + off);
+            vn = *(const vec8*)((const char*)lvb + off);
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
           }
-          sA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[dd], sA, 0, 0, 0);
+          sA = Tr::mfma(kf, qf[dd], sA);
           dpA =
-              __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[dd], dpA, 0, 0, 0);
+              Tr::mfma(vf, dof[dd], dpA);
           __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // MFMA x2
           kf = kn;
           vf = vn;
@@ -944,8 +948,8 @@ void ffa_bwd_dq_kernel(BwdParams p) {
       }
 
       // ---- dq += dS K (B-frags from the transposed K tile) ----
-      bf16x8 dsa0 = cframe_to_afrag(dsv, 0);
-      bf16x8 dsa1 = cframe_to_afrag(dsv, 1);
+      vec8 dsa0 = Tr::afrag(dsv, 0);
+      vec8 dsa1 = Tr::afrag(dsv, 1);
       // B-frags (B[kk=k][j=d]) via tr16 straight off the K row image
       // (same recipe as the dkv kernel)
       {
@@ -969,24 +973,23 @@ void ffa_bwd_dq_kernel(BwdParams p) {
         // serialized read->wait->mfma form parks the wave per fragment).
         // The sched_group_barriers hold the order: without them the
         // scheduler sinks each tr16 pair back in front of its own MFMA.
-        bf16x8 bcur = tr16_frag(k_base + rb0 + ((16 * qhalf2 * 2) ^ sw0),
+        vec8 bcur = Tr::tr16(k_base + rb0 + ((16 * qhalf2 * 2) ^ sw0),
                                 k_base + rb1 + ((16 * qhalf2 * 2) ^ sw1));
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read x2
 #pragma unroll
         for (int j = 0; j < 2 * DT; ++j) {
-          bf16x8 bnext = bcur;
+          vec8 bnext = bcur;
           if (j + 1 < 2 * DT) {
             const int dcoln = (((j + 1) >> 1) * 32 + 16 * qhalf2) * 2;
             if ((j + 1) & 1)
-              bnext = tr16_frag(k_base + rb2 + (dcoln ^ sw2),
+              bnext = Tr::tr16(k_base + rb2 + (dcoln ^ sw2),
                                 k_base + rb3 + (dcoln ^ sw3));
             else
-              bnext = tr16_frag(k_base + rb0 + (dcoln ^ sw0),
+              bnext = Tr::tr16(k_base + rb0 + (dcoln ^ sw0),
                                 k_base + rb1 + (dcoln ^ sw1));
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
           }
-          acc_dq[j >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              (j & 1) ? dsa1 : dsa0, bcur, acc_dq[j >> 1], 0, 0, 0);
+          acc_dq[j >> 1] = Tr::mfma((j & 1) ? dsa1 : dsa0, bcur, acc_dq[j >> 1]);
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA x1
           bcur = bnext;
         }
@@ -1020,10 +1023,17 @@ void ffa_bwd_dq_kernel(BwdParams p) {
 
 
 // ---------------- launchers ----------------
-extern "C" int magi_ffa_bwd_preprocess(const magi_ffa_bwd_args* a) {
+// Every entry is a template over the element type behind one extern "C"
+// function that picks the instantiation from args->elem_type.
+#define BY_ELEM_TYPE(a, fn)                                            \
+  ((a) && (a)->elem_type == MAGI_FFA_ELEM_FP16 ? fn<f16_t>(a) : fn<bf16_t>(a))
+
+template <class ET>
+static int bwd_preprocess(const magi_ffa_bwd_args* a) {
   if (!a || !a->dout || !a->out || !a->dpsum) return -1;
-  BwdParams p{};
-  p.dout = (const bf16_t*)a->dout;
+  if (!elem_type_known(a->elem_type)) return -9;
+  BwdParams<ET> p{};
+  p.dout = (const ET*)a->dout;
   p.out = a->out;
   p.dpsum = a->dpsum;
   const long long n_rows = a->total_q * a->hq;
@@ -1031,23 +1041,29 @@ extern "C" int magi_ffa_bwd_preprocess(const magi_ffa_bwd_args* a) {
   dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
   hipStream_t s = (hipStream_t)a->stream;
   if (a->out_is_fp32)
-    hipLaunchKernelGGL((bwd_preprocess_kernel<true>), grid, block, 0, s, p,
-                       a->d, n_rows);
+    hipLaunchKernelGGL((bwd_preprocess_kernel<ET, true>), grid, block, 0, s,
+                       p, a->d, n_rows);
   else
-    hipLaunchKernelGGL((bwd_preprocess_kernel<false>), grid, block, 0, s, p,
-                       a->d, n_rows);
+    hipLaunchKernelGGL((bwd_preprocess_kernel<ET, false>), grid, block, 0, s,
+                       p, a->d, n_rows);
   return (int)hipGetLastError();
 }
 
-static int fill_bwd_params(const magi_ffa_bwd_args* a, BwdParams* p) {
+extern "C" int magi_ffa_bwd_preprocess(const magi_ffa_bwd_args* a) {
+  return BY_ELEM_TYPE(a, bwd_preprocess);
+}
+
+template <class ET>
+static int fill_bwd_params(const magi_ffa_bwd_args* a, BwdParams<ET>* p) {
   if (!a || !a->dout || !a->q || !a->k || !a->v || !a->lse) return -1;
   if (a->d != 64 && a->d != 128 && a->d != 192) return -2;
   if (a->hq % a->hk != 0) return -3;
+  if (!elem_type_known(a->elem_type)) return -9;
   if (a->n_ranges <= 0) return 1;  // caller treats >0 as "nothing to do"
-  p->dout = (const bf16_t*)a->dout;
-  p->q = (const bf16_t*)a->q;
-  p->k = (const bf16_t*)a->k;
-  p->v = (const bf16_t*)a->v;
+  p->dout = (const ET*)a->dout;
+  p->q = (const ET*)a->q;
+  p->k = (const ET*)a->k;
+  p->v = (const ET*)a->v;
   p->out = a->out;
   p->lse = a->lse;
   p->dq = a->dq;
@@ -1116,12 +1132,12 @@ static BwdKnobs dq_knobs(const magi_ffa_bwd_args* a) {
           env_int("MAGI_BWD_DQ_BIGSEQ", 8192)};
 }
 
-template <int D>
+template <class ET, int D>
 static void launch_dq(int waves, bool sc, dim3 grid, hipStream_t s,
-                      const BwdParams& p) {
-#define GO(SC, W)                                                          \
-  hipLaunchKernelGGL((ffa_bwd_dq_kernel<D, SC, W>), grid, dim3(64 * W), 0, \
-                     s, p)
+                      const BwdParams<ET>& p) {
+#define GO(SC, W)                                                        \
+  hipLaunchKernelGGL((ffa_bwd_dq_kernel<ET, D, SC, W>), grid,            \
+                     dim3(64 * W), 0, s, p)
   if constexpr (D != 192) {  // D=192 spills at 8 waves: 4-wave builds only
     if (waves == 8) {
       if (sc) GO(true, 8); else GO(false, 8);
@@ -1132,8 +1148,9 @@ static void launch_dq(int waves, bool sc, dim3 grid, hipStream_t s,
 #undef GO
 }
 
-extern "C" int magi_ffa_bwd_dq(const magi_ffa_bwd_args* a) {
-  BwdParams p;
+template <class ET>
+static int bwd_dq(const magi_ffa_bwd_args* a) {
+  BwdParams<ET> p;
   int rc = fill_bwd_params(a, &p);
   if (rc) return rc > 0 ? 0 : rc;
   const BwdKnobs knobs = dq_knobs(a);
@@ -1148,10 +1165,14 @@ extern "C" int magi_ffa_bwd_dq(const magi_ffa_bwd_args* a) {
   grid = cap_grid(grid, a->cu_margin & 0xFFFF, W == 4 ? 2 : 1);
   hipStream_t s = (hipStream_t)a->stream;
   const bool sc = a->softcap > 0.f;
-  if (a->d == 64) launch_dq<64>(W, sc, grid, s, p);
-  else if (a->d == 192) launch_dq<192>(W, sc, grid, s, p);
-  else launch_dq<128>(W, sc, grid, s, p);
+  if (a->d == 64) launch_dq<ET, 64>(W, sc, grid, s, p);
+  else if (a->d == 192) launch_dq<ET, 192>(W, sc, grid, s, p);
+  else launch_dq<ET, 128>(W, sc, grid, s, p);
   return (int)hipGetLastError();
+}
+
+extern "C" int magi_ffa_bwd_dq(const magi_ffa_bwd_args* a) {
+  return BY_ELEM_TYPE(a, bwd_dq);
 }
 
 static BwdKnobs dkv_knobs() {
@@ -1167,11 +1188,11 @@ static BwdKnobs dkv_knobs() {
   return {env_int("MAGI_BWD_HEAD_MAJOR", 1), env_int("MAGI_BWD_BIGSEQ", 1024)};
 }
 
-template <int D, int MODE>
+template <class ET, int D, int MODE>
 static void launch_dkv(int waves, bool sc, dim3 grid, hipStream_t s,
-                       const BwdParams& p) {
+                       const BwdParams<ET>& p) {
 #define GO(SC, W)                                                        \
-  hipLaunchKernelGGL((ffa_bwd_dkv_kernel<D, SC, MODE, W>), grid,         \
+  hipLaunchKernelGGL((ffa_bwd_dkv_kernel<ET, D, SC, MODE, W>), grid,     \
                      dim3(64 * W), 0, s, p)
   if constexpr (D != 192) {  // D=192 spills at 8 waves: 4-wave builds only
     if (waves == 8) {
@@ -1183,9 +1204,9 @@ static void launch_dkv(int waves, bool sc, dim3 grid, hipStream_t s,
 #undef GO
 }
 
-template <int MODE>
+template <class ET, int MODE>
 static int launch_bwd_dkv(const magi_ffa_bwd_args* a) {
-  BwdParams p;
+  BwdParams<ET> p;
   int rc = fill_bwd_params(a, &p);
   if (rc) return rc > 0 ? 0 : rc;
   const BwdKnobs knobs = dkv_knobs();
@@ -1203,24 +1224,34 @@ static int launch_bwd_dkv(const magi_ffa_bwd_args* a) {
     grid = cap_grid(grid, a->cu_margin & 0xFFFF, W == 4 ? 2 : 1);
   hipStream_t s = (hipStream_t)a->stream;
   const bool sc = a->softcap > 0.f;
-  if (a->d == 64) launch_dkv<64, MODE>(W, sc, grid, s, p);
+  if (a->d == 64) launch_dkv<ET, 64, MODE>(W, sc, grid, s, p);
   else if (a->d == 192) {
-    if constexpr (MODE != 0) launch_dkv<192, MODE>(W, sc, grid, s, p);
+    if constexpr (MODE != 0) launch_dkv<ET, 192, MODE>(W, sc, grid, s, p);
     else return -6;  // fused + D=192 exceeds LDS; host routes to the split
-  } else launch_dkv<128, MODE>(W, sc, grid, s, p);
+  } else launch_dkv<ET, 128, MODE>(W, sc, grid, s, p);
   return (int)hipGetLastError();
 }
 
+template <class ET> static int bwd_dkv(const magi_ffa_bwd_args* a) {
+  return launch_bwd_dkv<ET, 0>(a);
+}
+template <class ET> static int bwd_dv(const magi_ffa_bwd_args* a) {
+  return launch_bwd_dkv<ET, 1>(a);
+}
+template <class ET> static int bwd_dk(const magi_ffa_bwd_args* a) {
+  return launch_bwd_dkv<ET, 2>(a);
+}
+
 extern "C" int magi_ffa_bwd_dkv(const magi_ffa_bwd_args* a) {
-  return launch_bwd_dkv<0>(a);
+  return BY_ELEM_TYPE(a, bwd_dkv);
 }
 
 extern "C" int magi_ffa_bwd_dv(const magi_ffa_bwd_args* a) {
-  return launch_bwd_dkv<1>(a);
+  return BY_ELEM_TYPE(a, bwd_dv);
 }
 
 extern "C" int magi_ffa_bwd_dk(const magi_ffa_bwd_args* a) {
-  return launch_bwd_dkv<2>(a);
+  return BY_ELEM_TYPE(a, bwd_dk);
 }
 
 extern "C" int magi_ffa_bwd(const magi_ffa_bwd_args* a) {

@@ -220,6 +220,85 @@ DEV_INLINE bf16x8 cframe_to_afrag(const float* val, int tt) {
   return cvt.v;
 }
 
+// ---- element type of the dense kernels (ffa_fwd.hip, ffa_bwd.hip) ----
+// Everything that differs between bf16 and fp16 q/k/v/dout: the fragment
+// vector, the 32x32x16 MFMA, the packed f32 -> 16-bit convert and the scalar
+// converts of the epilogues. Staging, swizzles and LDS layouts work in bytes
+// and the softmax in fp32, so they are shared. The bf16 members are the
+// helpers above, unchanged.
+using f16_t = _Float16;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+
+// RNE like pack_bf16_pair (the mode register's default rounding); results
+// below the smallest fp16 subnormal (2^-24) flush to zero
+DEV_INLINE unsigned pack_f16_pair(float lo, float hi) {
+  unsigned r;
+  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+
+template <class T>
+struct ElemTraits;
+
+template <>
+struct ElemTraits<bf16_t> {
+  using x8 = bf16x8;
+  static DEV_INLINE f32x16 mfma(x8 a, x8 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  }
+  static DEV_INLINE unsigned pack_pair(float lo, float hi) {
+    return pack_bf16_pair(lo, hi);
+  }
+  static DEV_INLINE x8 tr16(int a0, int a1) { return tr16_frag(a0, a1); }
+  static DEV_INLINE x8 afrag(const float* val, int tt) {
+    return cframe_to_afrag(val, tt);
+  }
+  static DEV_INLINE float to_f32(bf16_t x) { return (float)x; }
+  static DEV_INLINE bf16_t from_f32(float x) { return (bf16_t)x; }
+};
+
+template <>
+struct ElemTraits<f16_t> {
+  using x8 = f16x8;
+  static DEV_INLINE f32x16 mfma(x8 a, x8 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+  }
+  static DEV_INLINE unsigned pack_pair(float lo, float hi) {
+    return pack_f16_pair(lo, hi);
+  }
+  // ds_read_b64_tr_b16 moves 16-bit lanes whatever they hold
+  static DEV_INLINE x8 tr16(int a0, int a1) {
+    return __builtin_bit_cast(x8, tr16_frag(a0, a1));
+  }
+  // cframe_to_afrag with the fp16 packed convert
+  static DEV_INLINE x8 afrag(const float* val, int tt) {
+    unsigned c0 = pack_f16_pair(val[8 * tt + 0], val[8 * tt + 1]);
+    unsigned c1 = pack_f16_pair(val[8 * tt + 2], val[8 * tt + 3]);
+    unsigned c2 = pack_f16_pair(val[8 * tt + 4], val[8 * tt + 5]);
+    unsigned c3 = pack_f16_pair(val[8 * tt + 6], val[8 * tt + 7]);
+    auto r02 = __builtin_amdgcn_permlane32_swap(c0, c2, false, false);
+    auto r13 = __builtin_amdgcn_permlane32_swap(c1, c3, false, false);
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4_;
+    const u32x4_ u = {r02[0], r13[0], r02[1], r13[1]};
+    return __builtin_bit_cast(x8, u);
+  }
+  static DEV_INLINE float to_f32(f16_t x) { return (float)x; }
+  // The empty asm keeps x a finished f32: left visible, the compiler folds
+  // the epilogue's `acc * (1 / l)` into the convert as one v_fma_mixlo_f16,
+  // which rounds the exact product once. The direct store would then differ
+  // in the last bit from the f32 merge path cast to fp16, which rounds twice.
+  static DEV_INLINE f16_t from_f32(float x) {
+    asm("" : "+v"(x));
+    return (f16_t)x;
+  }
+};
+
+// elem_type of magi_ffa_fwd_args / magi_ffa_bwd_args names one of the two
+// (host side: the entries check it before any HIP call)
+static inline bool elem_type_known(int elem_type) {
+  return elem_type == MAGI_FFA_ELEM_BF16 || elem_type == MAGI_FFA_ELEM_FP16;
+}
+
 // ---- fp8 (OCP e4m3) helpers shared by ffa_fwd_fp8.hip / ffa_index_fp8.hip ----
 
 // f32 -> e4m3 via the packed convert (lower byte)

@@ -39,12 +39,14 @@
 #define FFA_BN 32    // k rows per inner tile
 #define LOCK_GRAN 128
 
+// ET: element type of q/k/v and of a 16-bit out, bf16_t or f16_t
+template <class ET>
 struct FwdParams {
-  const bf16_t* q;
-  const bf16_t* k;
-  const bf16_t* v;
-  float* out_f32;     // used when OUT_BF16==false
-  bf16_t* out_bf16;   // used when OUT_BF16==true
+  const ET* q;
+  const ET* k;
+  const ET* v;
+  float* out_f32;     // used when OUT_16==false
+  ET* out_16;         // used when OUT_16==true
   float* lse;
   const int* q_ranges;
   const int* k_ranges;
@@ -66,9 +68,13 @@ struct FwdParams {
 // WAVES: q-tiles per workgroup sharing ONE staged K/V image (see the bwd
 // kernels): 8 waves (one 512-thread WG/CU = 2 waves/SIMD) halve the staging
 // and barrier cost per MFMA for long ranges; 4 for short ranges.
-template <int D, bool HAS_SOFTCAP, bool ATOMIC, bool OUT_BF16, int WAVES,
-          int NBUF = 2>
-__global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParams p) {
+// ET: bf16_t or f16_t (ElemTraits, ffa_device.h); P is rounded to ET before PV.
+template <class ET, int D, bool HAS_SOFTCAP, bool ATOMIC, bool OUT_16,
+          int WAVES, int NBUF = 2>
+__global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
+    FwdParams<ET> p) {
+  using Tr = ElemTraits<ET>;
+  using vec8 = typename Tr::x8;
   constexpr int DF = D / 16;    // # of 16-wide d fragments
   constexpr int DT = D / 32;    // # of 32-wide output d tiles
   // Adaptive grid: head-major (blockIdx.x = head -> one XCD per head: L2
@@ -175,26 +181,26 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
   // The barrier's counted wait is the only vector-memory wait in the k loop.
   constexpr int KITER = 2 * FFA_BN;
   __shared__ __attribute__((aligned(16))) char fsmem[NBUF * 2 * KITER * ROWB];
-  auto lds_k = [&](int buf) -> __bf16* {
-    return (__bf16*)(fsmem + (2 * buf) * KITER * ROWB);
+  auto lds_k = [&](int buf) -> ET* {
+    return (ET*)(fsmem + (2 * buf) * KITER * ROWB);
   };
-  auto lds_v = [&](int buf) -> __bf16* {
-    return (__bf16*)(fsmem + (2 * buf + 1) * KITER * ROWB);
+  auto lds_v = [&](int buf) -> ET* {
+    return (ET*)(fsmem + (2 * buf + 1) * KITER * ROWB);
   };
 
-  // Q fragments in registers (8 x bf16x8 for D=128)
-  bf16x8 qf[DF];
+  // Q fragments in registers (8 x vec8 for D=128)
+  vec8 qf[DF];
   {
-    const bf16_t* qp = p.q + (size_t)qclamp * p.hq * D + (size_t)h * D;
+    const ET* qp = p.q + (size_t)qclamp * p.hq * D + (size_t)h * D;
 #pragma unroll
     for (int dd = 0; dd < DF; ++dd)
-      qf[dd] = *(const bf16x8*)(qp + dd * 16 + hi * 8);
+      qf[dd] = *(const vec8*)(qp + dd * 16 + hi * 8);
   }
 
   const int kh = h / p.gqa;
   const size_t k_pitch = (size_t)p.hk * D;
-  const bf16_t* kbase = p.k + (size_t)kh * D;
-  const bf16_t* vbase = p.v + (size_t)kh * D;
+  const ET* kbase = p.k + (size_t)kh * D;
+  const ET* vbase = p.v + (size_t)kh * D;
 
   float m_run = -INFINITY;
   float l_run = 0.f;
@@ -229,7 +235,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
 
   int cur = 0;
 
-  auto sub_body = [&](int ns, const __bf16* lkb, const __bf16* lvb) {
+  auto sub_body = [&](int ns, const ET* lkb, const ET* lvb) {
     const bool live = (ns + FFA_BN > n_lo) && (ns < n_hi) && qvalid_any;
     if (!live) return;
 
@@ -237,9 +243,9 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
     {
 #pragma unroll
       for (int dd = 0; dd < DF; ++dd) {
-        bf16x8 kf = *(const bf16x8*)(
+        vec8 kf = *(const vec8*)(
             (const char*)lkb + swz(lo32, lo32 * ROWB + dd * 32 + hi * 16));
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[dd], s, 0, 0, 0);
+        s = Tr::mfma(kf, qf[dd], s);
       }
     }
 
@@ -323,10 +329,10 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
       }
     }
 
-    // ---- P -> bf16 A-fragments (cvt_pk + permlane32_swap) ----
-    bf16x8 pa[2];
+    // ---- P -> 16-bit A-fragments (cvt_pk + permlane32_swap) ----
+    vec8 pa[2];
 #pragma unroll
-    for (int tt = 0; tt < 2; ++tt) pa[tt] = cframe_to_afrag(pr, tt);
+    for (int tt = 0; tt < 2; ++tt) pa[tt] = Tr::afrag(pr, tt);
 
     // ---- PV: B-frags via ds_read_b64_tr_b16 off the V row image ----
     {
@@ -349,19 +355,18 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
         const int rb0 = v_base + row0 * ROWB + lane8;
         const int rb1 = v_base + row1 * ROWB + lane8;
         const int dcol = (dt * 32 + 16 * qhalf) * 2;
-        return tr16_frag(rb0 + (dcol ^ sw0), rb1 + (dcol ^ sw1));
+        return Tr::tr16(rb0 + (dcol ^ sw0), rb1 + (dcol ^ sw1));
       };
-      bf16x8 bcur = vfrag(0);
+      vec8 bcur = vfrag(0);
       __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read x2
 #pragma unroll
       for (int j = 0; j < 2 * DT; ++j) {
-        bf16x8 bnext = bcur;
+        vec8 bnext = bcur;
         if (j + 1 < 2 * DT) {
           bnext = vfrag(j + 1);
           __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         }
-        acc_o[j % DT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            pa[j / DT], bcur, acc_o[j % DT], 0, 0, 0);
+        acc_o[j % DT] = Tr::mfma(pa[j / DT], bcur, acc_o[j % DT]);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA x1
         bcur = bnext;
       }
@@ -454,8 +459,8 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(FwdParam
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         const float val = acc_o[dt][r] * ilq;
-        if (OUT_BF16)
-          p.out_bf16[base + dt * 32 + lo32] = (bf16_t)val;
+        if (OUT_16)
+          p.out_16[base + dt * 32 + lo32] = Tr::from_f32(val);
         else
           p.out_f32[base + dt * 32 + lo32] = val;
       }
@@ -578,20 +583,20 @@ extern "C" int magi_probe_mfma(const void* a, const void* b, void* d,
 // ------------------------------------------------------------------
 // launcher
 // ------------------------------------------------------------------
-template <int D, int W, int NB>
-static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams& p,
+template <class ET, int D, int W, int NB>
+static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams<ET>& p,
                         dim3 grid, dim3 block, hipStream_t stream) {
   const bool sc = a->softcap > 0.f;
   const bool atomic = !a->disable_atomic_reduction;
-  const bool obf16 = !a->out_is_fp32;
-  if (atomic && obf16) return -10;  // atomic merge requires fp32 out
+  const bool o16 = !a->out_is_fp32;
+  if (atomic && o16) return -10;  // atomic merge requires fp32 out
 #define LAUNCH(SC, AT, OB)                                                 \
-  hipLaunchKernelGGL((ffa_fwd_kernel<D, SC, AT, OB, W, NB>), grid, block,  \
-                     0, stream, p)
+  hipLaunchKernelGGL((ffa_fwd_kernel<ET, D, SC, AT, OB, W, NB>), grid,     \
+                     block, 0, stream, p)
   if (atomic) {
     if (sc) LAUNCH(true, true, false);
     else LAUNCH(false, true, false);
-  } else if (obf16) {
+  } else if (o16) {
     if (sc) LAUNCH(true, false, true);
     else LAUNCH(false, false, true);
   } else {
@@ -602,19 +607,15 @@ static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams& p,
   return (int)hipGetLastError();
 }
 
-extern "C" int magi_ffa_fwd(const magi_ffa_fwd_args* a) {
-  if (!a || !a->q || !a->k || !a->v || !a->out || !a->lse) return -1;
-  if (a->d != 64 && a->d != 128 && a->d != 192) return -2;
-  if (a->hq % a->hk != 0) return -3;
-  if (a->n_ranges <= 0) return 0;
-  if (!a->disable_atomic_reduction && !a->locks) return -4;
-
-  FwdParams p;
-  p.q = (const bf16_t*)a->q;
-  p.k = (const bf16_t*)a->k;
-  p.v = (const bf16_t*)a->v;
+// magi_ffa_fwd past its validation, for one element type
+template <class ET>
+static int fwd_entry(const magi_ffa_fwd_args* a) {
+  FwdParams<ET> p;
+  p.q = (const ET*)a->q;
+  p.k = (const ET*)a->k;
+  p.v = (const ET*)a->v;
   p.out_f32 = (float*)a->out;
-  p.out_bf16 = (bf16_t*)a->out;
+  p.out_16 = (ET*)a->out;
   p.lse = a->lse;
   p.q_ranges = a->q_ranges;
   p.k_ranges = a->k_ranges;
@@ -672,17 +673,43 @@ extern "C" int magi_ffa_fwd(const magi_ffa_fwd_args* a) {
   int nbuf = 3;
   { const char* e = getenv("MAGI_FWD_NBUF"); if (e) nbuf = atoi(e); }
   if (a->d == 64)
-    return fw == 8 ? (nbuf == 3
-                          ? launch_fwd_d<64, 8, 3>(a, p, grid, block, stream)
-                          : launch_fwd_d<64, 8, 2>(a, p, grid, block, stream))
-                   : launch_fwd_d<64, 4, 2>(a, p, grid, block, stream);
+    return fw == 8
+               ? (nbuf == 3
+                      ? launch_fwd_d<ET, 64, 8, 3>(a, p, grid, block, stream)
+                      : launch_fwd_d<ET, 64, 8, 2>(a, p, grid, block, stream))
+               : launch_fwd_d<ET, 64, 4, 2>(a, p, grid, block, stream);
   if (a->d == 192)
-    return fw == 8 ? launch_fwd_d<192, 8, 2>(a, p, grid, block, stream)
-                   : launch_fwd_d<192, 4, 2>(a, p, grid, block, stream);
-  return fw == 8 ? (nbuf == 3
-                        ? launch_fwd_d<128, 8, 3>(a, p, grid, block, stream)
-                        : launch_fwd_d<128, 8, 2>(a, p, grid, block, stream))
-               : launch_fwd_d<128, 4, 2>(a, p, grid, block, stream);
+    return fw == 8 ? launch_fwd_d<ET, 192, 8, 2>(a, p, grid, block, stream)
+                   : launch_fwd_d<ET, 192, 4, 2>(a, p, grid, block, stream);
+  return fw == 8
+             ? (nbuf == 3
+                    ? launch_fwd_d<ET, 128, 8, 3>(a, p, grid, block, stream)
+                    : launch_fwd_d<ET, 128, 8, 2>(a, p, grid, block, stream))
+             : launch_fwd_d<ET, 128, 4, 2>(a, p, grid, block, stream);
+}
+
+extern "C" int magi_ffa_fwd(const magi_ffa_fwd_args* a) {
+  if (!a || !a->q || !a->k || !a->v || !a->out || !a->lse) return -1;
+  if (a->d != 64 && a->d != 128 && a->d != 192) return -2;
+  if (a->hq % a->hk != 0) return -3;
+  if (!elem_type_known(a->elem_type)) return -9;
+  if (a->n_ranges <= 0) return 0;
+  if (!a->disable_atomic_reduction && !a->locks) return -4;
+  return a->elem_type == MAGI_FFA_ELEM_FP16 ? fwd_entry<f16_t>(a)
+                                            : fwd_entry<bf16_t>(a);
+}
+
+extern "C" int magi_ffa_args_size(int which) {
+  switch (which) {
+    case 0: return (int)sizeof(magi_ffa_fwd_args);
+    case 1: return (int)sizeof(magi_ffa_bwd_args);
+    case 2: return (int)sizeof(magi_range_op_args);
+    case 3: return (int)sizeof(magi_sink_args);
+    case 4: return (int)sizeof(magi_correct_args);
+    case 5: return (int)sizeof(magi_ffa_index_args);
+    case 6: return (int)sizeof(magi_ffa_index_bwd_args);
+    default: return -1;
+  }
 }
 
 extern "C" int magi_ffa_abi_version(void) { return 1; }

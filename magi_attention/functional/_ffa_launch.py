@@ -141,7 +141,8 @@ def bwd_dsink(sink_f, s_sink, ssh, lse, dpsum, dsink=None) -> torch.Tensor:
 def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
         max_logits, qk_starts, max_seqlen_q, softmax_scale, softcap,
         disable_fwd_atomic_reduction, sm_margin, deterministic) -> None:
-    """Dense forward into (out, lse): the bf16 or the fp8 entry by q.dtype;
+    """Dense forward into (out, lse): the fp8 entry or the 16-bit one (bf16 or
+    fp16 by elem_type) by q.dtype;
     deterministic = fixed merge order, one launch per q-disjoint range group."""
     tq, hq, d = q.shape
     tk, hk, _ = k.shape
@@ -156,6 +157,7 @@ def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
         out_is_fp32=int(out.dtype == torch.float32),
         disable_atomic_reduction=int(disable_fwd_atomic_reduction),
         cu_margin=sm_margin, stream=current_stream_ptr(),
+        elem_type=_ffa_lib.elem_type_of(q.dtype),
     )
     lib = _ffa_lib.lib()
     fn = lib.magi_ffa_fwd_fp8 if q.dtype == _FP8 else lib.magi_ffa_fwd
@@ -174,7 +176,8 @@ def bwd_args(dout, out, dpsum, *, q=None, k=None, v=None, lse=None,
              softcap=0.0, sm_margin=0) -> _ffa_lib.MagiFfaBwdArgs:
     """The backward argument struct. (dout, out, dpsum) are all the dpsum
     preprocess reads; the dq/dk/dv passes need every member. The tensors must
-    be contiguous and outlive the launches."""
+    be contiguous and outlive the launches. dout's dtype (bf16 or fp16) is the
+    element type of q/k/v too, and of a 16-bit out."""
     tq, hq, d = dout.shape
     tk, hk = (0, 0) if k is None else k.shape[:2]
     return _ffa_lib.MagiFfaBwdArgs(
@@ -187,6 +190,7 @@ def bwd_args(dout, out, dpsum, *, q=None, k=None, v=None, lse=None,
         out_is_fp32=int(out.dtype == torch.float32),
         softmax_scale=softmax_scale, softcap=softcap,
         cu_margin=sm_margin, stream=current_stream_ptr(),
+        elem_type=_ffa_lib.elem_type_of(dout.dtype),
     )
 
 

@@ -253,6 +253,7 @@ class DistAttnRuntime:
         in_dtype = q.dtype
         # same fp8 backward policy as the single-GPU wrapper
         q, k, v, out, dout = _ffa_launch.upcast_fp8(q, k, v, out, dout)
+        dout = dout.to(q.dtype)  # the kernels read dout as q's element type
 
         dq_acc = torch.zeros(tq, hq, d, dtype=torch.float32, device=q.device)
         dkv_acc = torch.zeros(2 * L, *k.shape[1:], dtype=torch.float32,

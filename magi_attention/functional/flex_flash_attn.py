@@ -121,24 +121,49 @@ def _flex_flash_attn_forward(
     qk_starts: Optional[torch.Tensor] = None,
     **_unused,
 ) -> tuple[torch.Tensor, AttnForwardMeta]:
+    """Dense (range-table) forward into (out, lse). q/k/v are all bf16, all
+    fp16 or all fp8-e4m3. In merge mode out is an f32 accumulator; with
+    disable_fwd_atomic_reduction it defaults to q's dtype, stored directly by
+    the kernel, and a 16-bit out or out_type must be q's own 16-bit type.
+
+    fp16 direct store with a sink: the sink postprocess kernel reads a 16-bit
+    out as bf16, so it must never see fp16. That combination therefore runs
+    the kernel into an f32 out, applies the sink there, and casts to fp16
+    once at the end (into the caller's out if one was given); lse is
+    unaffected."""
     is_fp8 = q.dtype == torch.float8_e4m3fn
-    assert q.dtype in (torch.bfloat16, torch.float8_e4m3fn), (
-        "bf16 or fp8-e4m3 inputs"
+    assert q.dtype in (torch.bfloat16, torch.float16, torch.float8_e4m3fn), (
+        "bf16, fp16 or fp8-e4m3 inputs"
     )
-    # the kernel is picked from q.dtype alone and reads k and v at q's
-    # element size: a mixed call would run past the end of the narrower buffers
+    # the kernel is picked from q.dtype alone and reads k and v as q's element
+    # type: a mixed call would run past the end of the narrower buffers, or
+    # read fp16 bits as bf16
     assert k.dtype == q.dtype and v.dtype == q.dtype, (
-        "flex_flash_attn q, k and v must all be fp8-e4m3 or all be bf16, got "
-        f"q={q.dtype}, k={k.dtype}, v={v.dtype}"
+        "flex_flash_attn q, k and v must all be fp8-e4m3 or all be bf16 (or "
+        f"all be fp16), got q={q.dtype}, k={k.dtype}, v={v.dtype}"
     )
+    for what, t in (("out", None if out is None else out.dtype),
+                    ("out_type", out_type)):
+        assert t in (None, torch.float32) or t == (
+            torch.bfloat16 if is_fp8 else q.dtype
+        ), f"{what} {t} must be float32 or q's own 16-bit type, q={q.dtype}"
     q, k, v, q_ranges, k_ranges, attn_type_map = map(
         maybe_contiguous, (q, k, v, q_ranges, k_ranges, attn_type_map)
     )
 
     tq, hq, d = q.shape
 
+    dtype = out.dtype if out is not None else out_type or (
+        q.dtype if disable_fwd_atomic_reduction else torch.float32
+    )
+    # fp16 direct store + sink: f32 out through the sink, one cast at the end
+    via_f32 = (sink is not None and disable_fwd_atomic_reduction
+               and dtype == torch.float16)
+    out_f16 = out if via_f32 else None
+    if via_f32:
+        out = None if out is None else out.float()
+        dtype = torch.float32
     if out is None:
-        dtype = out_type or (q.dtype if disable_fwd_atomic_reduction else torch.float32)
         out = torch.zeros(tq, hq, d, dtype=dtype, device=q.device)
     if lse is None:
         lse = torch.full((tq, hq), float("-inf"), dtype=torch.float32, device=q.device)
@@ -148,7 +173,6 @@ def _flex_flash_attn_forward(
         assert out_is_fp32, "atomic (merge) forward requires an fp32 out accumulator"
         locks = _get_locks(tq, hq, q.device)
     else:
-        assert out.dtype in (torch.float32, torch.bfloat16)
         locks = None
 
     if max_seqlen_q is None:
@@ -170,7 +194,10 @@ def _flex_flash_attn_forward(
         sm_margin=sm_margin, deterministic=deterministic,
     )
     if sink is not None:
+        assert out.dtype != torch.float16  # the postprocess reads 16 bits as bf16
         _apply_sink_postprocess(out, lse, sink, sink_layout, tq, hq, d)
+    if via_f32:
+        out = out.half() if out_f16 is None else out_f16.copy_(out)
     return out, AttnForwardMeta(lse=lse, max_logits=max_logits)
 
 
@@ -441,6 +468,11 @@ def _flex_flash_attn_backward(
         maybe_contiguous, (dout, q, k, v, out, q_ranges, k_ranges, attn_type_map)
     )
     tq, hq, _ = q.shape
+    # the kernels read dout, and a 16-bit out, as q's element type
+    assert q.dtype in (torch.bfloat16, torch.float16)
+    assert k.dtype == q.dtype and v.dtype == q.dtype
+    assert out.dtype in (torch.float32, q.dtype)
+    dout = dout.to(q.dtype)
 
     # fp32 accumulators, atomically reduced by the kernel
     dq = torch.zeros_like(q, dtype=torch.float32) if dq is None else dq
@@ -619,7 +651,14 @@ def flex_flash_attn_func(
     is differentiable (dsink in sink.dtype, f32 math, fp8 inputs included);
     meta.max_logits is the per-head f32 [hq] maximum scaled (softcapped)
     logit over valid slots (-inf if there is none), hq <= 128, and the sink
-    logits do not enter it."""
+    logits do not enter it.
+
+    On the range path q/k/v may also be all float16: out and the gradients
+    come back in fp16, lse / max_logits / dsink math stays f32, and every
+    option of the bf16 path applies (padded head dims, sink, softcap,
+    deterministic, auto_range_merge, direct store). P and dS are rounded to
+    fp16 before their MFMAs and accumulate in fp32. Mixed 16-bit dtypes are
+    rejected; index_attn_indices stays bf16 / fp8 only."""
     # ── sparse-input validation (mirrors reference :1344-1384) ──
     _has_ranges = q_ranges is not None
     _has_index = index_attn_indices is not None
@@ -708,7 +747,9 @@ def flex_flash_attn_func(
         # autograd pad). Reference buckets head_size <=64/<=128/<=192
         # (flash_api.cpp:322-334); the 192 bucket lands with a D=192 kernel.
         assert d < 192, f"head_dim {d} > 192 is beyond the reference's buckets"
-        assert q.dtype == torch.bfloat16, "padded head dims require bf16"
+        assert q.dtype in (torch.bfloat16, torch.float16), (
+            "padded head dims require bf16 or fp16"
+        )
         bucket = 64 if d <= 64 else (128 if d <= 128 else 192)
         if softmax_scale is None:
             softmax_scale = d ** (-0.5)  # scale from the REAL head dim
