@@ -82,9 +82,10 @@ typedef struct magi_ffa_bwd_args {
   const void* v;            /* elem_type [total_k, hk, d] */
   const void* out;          /* elem_type or f32 [total_q, hq, d] (forward output) */
   const float* lse;         /* f32 [total_q, hq] */
-  float* dq;                /* f32 [total_q, hq, d], zeroed, atomic-accumulated */
-  float* dk;                /* f32 [total_k, hk, d], zeroed, atomic-accumulated */
-  float* dv;                /* f32 [total_k, hk, d], zeroed, atomic-accumulated */
+  void* dq;                 /* [total_q, hq, d], zeroed: f32, atomic-accumulated
+                               (elem_type through the *_direct entries below) */
+  void* dk;                 /* [total_k, hk, d], as dq */
+  void* dv;                 /* [total_k, hk, d], as dq */
   float* dpsum;             /* f32 [total_q, hq] workspace = rowsum(dO*O) */
   const int32_t* q_ranges;  /* [n, 2] */
   const int32_t* k_ranges;  /* [n, 2] */
@@ -111,7 +112,8 @@ typedef struct magi_ffa_bwd_args {
 /* Every backward entry below (_preprocess, _dq, _dkv, _dv, _dk and
  * magi_ffa_bwd) returns -9 for an elem_type that is not one of
  * MAGI_FFA_ELEM_*, after its null-pointer (-1), head-dim (-2) and GQA (-3)
- * checks and before any HIP call. dq/dk/dv stay f32 for both element types. */
+ * checks and before any HIP call; then n_ranges <= 0 returns 0 without a
+ * launch. Through these entries dq/dk/dv are f32 for both element types. */
 
 /* dPsum preprocess: dpsum[t,h] = sum_d dout[t,h,d] * out[t,h,d]
  * (reference flash_bwd_preprocess_kernel.h:42). */
@@ -130,6 +132,43 @@ int magi_ffa_bwd_dkv(const magi_ffa_bwd_args* args);
 int magi_ffa_bwd_dv(const magi_ffa_bwd_args* args);
 int magi_ffa_bwd_dk(const magi_ffa_bwd_args* args);
 int magi_ffa_bwd(const magi_ffa_bwd_args* args);
+
+/* Direct 16-bit gradient stores for disjoint ranges. magi_ffa_bwd_args keeps
+ * its size and its last member (bindings check both), so the two switches
+ * ride behind an embedded copy of it, and the passes that honour them are
+ * entries of their own. With both members 0 an entry is its namesake above,
+ * bit for bit.
+ *   dq_is_16bit   1: args.dq is a zeroed elem_type buffer and the q ranges
+ *                 (the unique ones under seg_starts) are disjoint: the dq pass
+ *                 stores each register tile once, rounded to nearest even,
+ *                 with no atomics.
+ *   dkv_is_16bit  1: the same for args.dk and args.dv, the k ranges and the
+ *                 dkv / dv / dk passes; needs hq == hk.
+ * The direct stores write every row of a range that a live tile covers, zeros
+ * included, and nothing else: rows outside every range keep the caller's
+ * zeros, as with f32. The promised disjointness is not checked; where ranges
+ * do overlap the last writer wins. On single-owner input the stored value is
+ * numerically the f32 path's value cast to elem_type: the same bits, except
+ * that an exact -0 tile value is stored as -0 where the f32 path, which adds
+ * no zeros, leaves the caller's +0.
+ * Validation, in this order, all before any HIP call: -1 null pointer, -2
+ * head dim, -3 hq % hk != 0, -9 elem_type; then, in _dkv_direct, _dv_direct
+ * and _dk_direct with dkv_is_16bit set and whatever n_ranges is: -11 hq != hk
+ * (several q heads add into one dK/dV row), -12 a deterministic GQA head
+ * split packed into cu_margin's top 16 bits; then n_ranges <= 0 returns 0
+ * without a launch. magi_ffa_bwd_direct_args_size is sizeof of the struct as
+ * compiled (magi_ffa_args_size keeps its list). */
+typedef struct magi_ffa_bwd_direct_args {
+  magi_ffa_bwd_args args;
+  int32_t dq_is_16bit;
+  int32_t dkv_is_16bit;
+} magi_ffa_bwd_direct_args;
+
+int magi_ffa_bwd_dq_direct(const magi_ffa_bwd_direct_args* args);
+int magi_ffa_bwd_dkv_direct(const magi_ffa_bwd_direct_args* args);
+int magi_ffa_bwd_dv_direct(const magi_ffa_bwd_direct_args* args);
+int magi_ffa_bwd_dk_direct(const magi_ffa_bwd_direct_args* args);
+int magi_ffa_bwd_direct_args_size(void);
 
 /* ------------------------------------------------------------------ *
  * Range row ops (reference common/range_op/_range_*.py — Triton there,

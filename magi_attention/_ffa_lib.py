@@ -89,6 +89,20 @@ class MagiFfaBwdArgs(ctypes.Structure):
     ]
 
 
+class MagiFfaBwdDirectArgs(MagiFfaBwdArgs):
+    """mirrors magi_ffa_bwd_direct_args: magi_ffa_bwd_args embedded first
+    (ctypes appends a subclass's fields after its base's full size, as C does
+    for a struct member), then the two switches of the magi_ffa_bwd_*_direct
+    entries. An instance also passes as the MagiFfaBwdArgs it starts with."""
+
+    _fields_ = [
+        # 1: dq / dk and dv are buffers of the element type that the pass
+        # stores directly (disjoint ranges); 0: f32 atomic accumulators
+        ("dq_is_16bit", ctypes.c_int32),
+        ("dkv_is_16bit", ctypes.c_int32),
+    ]
+
+
 class MagiRangeOpArgs(ctypes.Structure):
     _fields_ = [
         ("input", ctypes.c_void_p),
@@ -244,6 +258,11 @@ def _try_load() -> ctypes.CDLL | None:
             ("magi_ffa_bwd_dv", [ctypes.POINTER(MagiFfaBwdArgs)]),
             ("magi_ffa_bwd_dk", [ctypes.POINTER(MagiFfaBwdArgs)]),
             ("magi_ffa_bwd_preprocess", [ctypes.POINTER(MagiFfaBwdArgs)]),
+            ("magi_ffa_bwd_dq_direct", [ctypes.POINTER(MagiFfaBwdDirectArgs)]),
+            ("magi_ffa_bwd_dkv_direct", [ctypes.POINTER(MagiFfaBwdDirectArgs)]),
+            ("magi_ffa_bwd_dv_direct", [ctypes.POINTER(MagiFfaBwdDirectArgs)]),
+            ("magi_ffa_bwd_dk_direct", [ctypes.POINTER(MagiFfaBwdDirectArgs)]),
+            ("magi_ffa_bwd_direct_args_size", []),
             ("magi_range_gather", [ctypes.POINTER(MagiRangeOpArgs)]),
             ("magi_range_reduce", [ctypes.POINTER(MagiRangeOpArgs)]),
             ("magi_correct_out_lse", [ctypes.POINTER(MagiCorrectArgs)]),

@@ -40,6 +40,11 @@
 // 8 waves (one 512-thread workgroup per CU, 2 waves/SIMD) serve long ranges,
 // 4 waves short ranges and D=192; the launchers at the end of the file pick.
 // The staging ring depth (NBUF) is fixed by (MODE, WAVES) inside each kernel.
+// Both mainloop kernels end in one of two epilogues, chosen at compile time:
+// DIRECT = false adds the register tile into a zeroed f32 buffer with atomics
+// (ranges may overlap, GQA heads share dK/dV rows); DIRECT = true rounds it to
+// the element type and stores it once with plain stores, for callers that
+// promise a single owner per element (the *_direct entries, magi_ffa.h).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -63,9 +68,9 @@ struct BwdParams {
   const ET* v;
   const void* out;
   const float* lse;
-  float* dq;
-  float* dk;
-  float* dv;
+  void* dq;   // f32 (atomic epilogue) or ET (direct epilogue), as dk and dv
+  void* dk;
+  void* dv;
   float* dpsum;
   const int* q_ranges;
   const int* k_ranges;
@@ -129,7 +134,8 @@ __global__ __launch_bounds__(256) void bwd_preprocess_kernel(BwdParams<ET> p,
 // 8-wave kernels run the 3-ring; the fused mode keeps 2 (its K/V tiles + a
 // 3-ring exceed the 160 KB LDS), and so do 4-wave workgroups (3 buffers
 // exceed the 80 KB/WG budget of 2 blocks/CU).
-template <class ET, int D, bool HAS_SOFTCAP, int MODE, int WAVES>
+// DIRECT: the epilogue (see the head of the file); nothing before it differs.
+template <class ET, int D, bool HAS_SOFTCAP, int MODE, int WAVES, bool DIRECT>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1)
 void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
   using Tr = ElemTraits<ET>;
@@ -663,12 +669,34 @@ void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
 
   // ---- write dK/dV ----
   if (wave_live) {
+  if constexpr (DIRECT) {
+    // single owner (disjoint k ranges, hq == hk): the rounded tile IS the
+    // row, zeros included - the number the atomic add into a zeroed f32
+    // buffer followed by a cast gives. from_f32 rounds the finished f32
+    // value. pin_vgpr on the dK tile in front of each row's converts changes
+    // no value; it steers the register allocator: without it the 8-wave
+    // d-128 dK-only kernel, which spills at the 256 cap, spills one dword
+    // more than its atomic twin (profiles/bwd_direct_store.md).
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int kr = n0 + crow(r, hi);
+      if (kr >= ke) continue;
+      ET* dkp = (ET*)p.dk + (size_t)kr * k_pitch + (size_t)kh * D + lo32;
+      ET* dvp = (ET*)p.dv + (size_t)kr * k_pitch + (size_t)kh * D + lo32;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        if constexpr (WANT_DK) pin_vgpr(acc_dk[dt]);
+        if constexpr (WANT_DK) dkp[dt * 32] = Tr::from_f32(acc_dk[dt][r]);
+        if constexpr (WANT_DV) dvp[dt * 32] = Tr::from_f32(acc_dv[dt][r]);
+      }
+    }
+  } else {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int kr = n0 + crow(r, hi);
     if (kr >= ke) continue;
-    float* dkp = p.dk + (size_t)kr * k_pitch + (size_t)kh * D;
-    float* dvp = p.dv + (size_t)kr * k_pitch + (size_t)kh * D;
+    float* dkp = (float*)p.dk + (size_t)kr * k_pitch + (size_t)kh * D;
+    float* dvp = (float*)p.dv + (size_t)kr * k_pitch + (size_t)kh * D;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       if constexpr (WANT_DK) {
@@ -680,6 +708,7 @@ void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
           unsafeAtomicAdd(dvp + dt * 32 + lo32, acc_dv[dt][r]);
       }
     }
+  }
   }
   }  // wave_live store
   if constexpr (MODE == 0) break;  // single trip: kills the backedge (regs)
@@ -698,7 +727,8 @@ void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
 // D=192 builds spill at 8 waves' 256-register cap and exist at 4 only).
 // 8 waves run the 3-slot staging ring (see the dkv kernel note); 4 waves keep
 // 2 slots (3 buffers exceed the 80 KB/WG budget of 2 blocks/CU).
-template <class ET, int D, bool HAS_SOFTCAP, int WAVES>
+// DIRECT: the epilogue (see the head of the file); nothing before it differs.
+template <class ET, int D, bool HAS_SOFTCAP, int WAVES, bool DIRECT>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 1 : 2)
 void ffa_bwd_dq_kernel(BwdParams<ET> p) {
   using Tr = ElemTraits<ET>;
@@ -1006,17 +1036,30 @@ void ffa_bwd_dq_kernel(BwdParams<ET> p) {
   __syncthreads();
   }  // seg
 
-  // ---- store dq once (atomicAdd: q_ranges of different slices may overlap) ----
+  // ---- store dq once (atomicAdd: q_ranges of different slices may overlap;
+  // DIRECT: the caller promises they do not, see the dkv epilogue) ----
+  if constexpr (DIRECT) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qr = m0 + crow(r, hi);
+      if (qr >= qe) continue;
+      ET* dst = (ET*)p.dq + (size_t)qr * q_pitch + (size_t)h * D + lo32;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt)
+        dst[dt * 32] = Tr::from_f32(acc_dq[dt][r]);
+    }
+  } else {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int qr = m0 + crow(r, hi);
     if (qr >= qe) continue;
-    float* dst = p.dq + (size_t)qr * q_pitch + (size_t)h * D;
+    float* dst = (float*)p.dq + (size_t)qr * q_pitch + (size_t)h * D;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       const float val = acc_dq[dt][r];
       if (val != 0.f) unsafeAtomicAdd(dst + dt * 32 + lo32, val);
     }
+  }
   }
   }  // strided work loop
 }
@@ -1025,8 +1068,9 @@ void ffa_bwd_dq_kernel(BwdParams<ET> p) {
 // ---------------- launchers ----------------
 // Every entry is a template over the element type behind one extern "C"
 // function that picks the instantiation from args->elem_type.
-#define BY_ELEM_TYPE(a, fn)                                            \
-  ((a) && (a)->elem_type == MAGI_FFA_ELEM_FP16 ? fn<f16_t>(a) : fn<bf16_t>(a))
+#define BY_ELEM_TYPE(a, fn, ...)                                       \
+  ((a) && (a)->elem_type == MAGI_FFA_ELEM_FP16 ? fn<f16_t>(a, ##__VA_ARGS__) \
+                                               : fn<bf16_t>(a, ##__VA_ARGS__))
 
 template <class ET>
 static int bwd_preprocess(const magi_ffa_bwd_args* a) {
@@ -1053,12 +1097,25 @@ extern "C" int magi_ffa_bwd_preprocess(const magi_ffa_bwd_args* a) {
   return BY_ELEM_TYPE(a, bwd_preprocess);
 }
 
-template <class ET>
-static int fill_bwd_params(const magi_ffa_bwd_args* a, BwdParams<ET>* p) {
+// Validation shared by the dq and dkv entries, in the order magi_ffa.h
+// documents; no HIP call before it. dkv_direct adds the rules of the direct
+// dK/dV store, which has no other head or launch adding into its rows.
+static int check_bwd_args(const magi_ffa_bwd_args* a, bool dkv_direct) {
   if (!a || !a->dout || !a->q || !a->k || !a->v || !a->lse) return -1;
   if (a->d != 64 && a->d != 128 && a->d != 192) return -2;
   if (a->hq % a->hk != 0) return -3;
   if (!elem_type_known(a->elem_type)) return -9;
+  if (dkv_direct) {
+    if (a->hq != a->hk) return -11;
+    if (a->cu_margin & 0xFFFF0000) return -12;
+  }
+  return 0;
+}
+
+template <class ET>
+static int fill_bwd_params(const magi_ffa_bwd_args* a, BwdParams<ET>* p,
+                           bool dkv_direct) {
+  if (const int rc = check_bwd_args(a, dkv_direct)) return rc;
   if (a->n_ranges <= 0) return 1;  // caller treats >0 as "nothing to do"
   p->dout = (const ET*)a->dout;
   p->q = (const ET*)a->q;
@@ -1132,11 +1189,11 @@ static BwdKnobs dq_knobs(const magi_ffa_bwd_args* a) {
           env_int("MAGI_BWD_DQ_BIGSEQ", 8192)};
 }
 
-template <class ET, int D>
+template <class ET, int D, bool DIRECT>
 static void launch_dq(int waves, bool sc, dim3 grid, hipStream_t s,
                       const BwdParams<ET>& p) {
 #define GO(SC, W)                                                        \
-  hipLaunchKernelGGL((ffa_bwd_dq_kernel<ET, D, SC, W>), grid,            \
+  hipLaunchKernelGGL((ffa_bwd_dq_kernel<ET, D, SC, W, DIRECT>), grid,    \
                      dim3(64 * W), 0, s, p)
   if constexpr (D != 192) {  // D=192 spills at 8 waves: 4-wave builds only
     if (waves == 8) {
@@ -1149,9 +1206,9 @@ static void launch_dq(int waves, bool sc, dim3 grid, hipStream_t s,
 }
 
 template <class ET>
-static int bwd_dq(const magi_ffa_bwd_args* a) {
+static int bwd_dq(const magi_ffa_bwd_args* a, bool direct_store) {
   BwdParams<ET> p;
-  int rc = fill_bwd_params(a, &p);
+  int rc = fill_bwd_params(a, &p, false);
   if (rc) return rc > 0 ? 0 : rc;
   const BwdKnobs knobs = dq_knobs(a);
   p.head_major = knobs.head_major;
@@ -1165,14 +1222,18 @@ static int bwd_dq(const magi_ffa_bwd_args* a) {
   grid = cap_grid(grid, a->cu_margin & 0xFFFF, W == 4 ? 2 : 1);
   hipStream_t s = (hipStream_t)a->stream;
   const bool sc = a->softcap > 0.f;
-  if (a->d == 64) launch_dq<ET, 64>(W, sc, grid, s, p);
-  else if (a->d == 192) launch_dq<ET, 192>(W, sc, grid, s, p);
-  else launch_dq<ET, 128>(W, sc, grid, s, p);
+  auto go = [&](auto direct) {
+    constexpr bool DIRECT = decltype(direct)::value;
+    if (a->d == 64) launch_dq<ET, 64, DIRECT>(W, sc, grid, s, p);
+    else if (a->d == 192) launch_dq<ET, 192, DIRECT>(W, sc, grid, s, p);
+    else launch_dq<ET, 128, DIRECT>(W, sc, grid, s, p);
+  };
+  if (direct_store) go(std::true_type{}); else go(std::false_type{});
   return (int)hipGetLastError();
 }
 
 extern "C" int magi_ffa_bwd_dq(const magi_ffa_bwd_args* a) {
-  return BY_ELEM_TYPE(a, bwd_dq);
+  return BY_ELEM_TYPE(a, bwd_dq, false);
 }
 
 static BwdKnobs dkv_knobs() {
@@ -1188,11 +1249,11 @@ static BwdKnobs dkv_knobs() {
   return {env_int("MAGI_BWD_HEAD_MAJOR", 1), env_int("MAGI_BWD_BIGSEQ", 1024)};
 }
 
-template <class ET, int D, int MODE>
+template <class ET, int D, int MODE, bool DIRECT>
 static void launch_dkv(int waves, bool sc, dim3 grid, hipStream_t s,
                        const BwdParams<ET>& p) {
-#define GO(SC, W)                                                        \
-  hipLaunchKernelGGL((ffa_bwd_dkv_kernel<ET, D, SC, MODE, W>), grid,     \
+#define GO(SC, W)                                                           \
+  hipLaunchKernelGGL((ffa_bwd_dkv_kernel<ET, D, SC, MODE, W, DIRECT>), grid, \
                      dim3(64 * W), 0, s, p)
   if constexpr (D != 192) {  // D=192 spills at 8 waves: 4-wave builds only
     if (waves == 8) {
@@ -1205,9 +1266,9 @@ static void launch_dkv(int waves, bool sc, dim3 grid, hipStream_t s,
 }
 
 template <class ET, int MODE>
-static int launch_bwd_dkv(const magi_ffa_bwd_args* a) {
+static int launch_bwd_dkv(const magi_ffa_bwd_args* a, bool direct_store) {
   BwdParams<ET> p;
-  int rc = fill_bwd_params(a, &p);
+  int rc = fill_bwd_params(a, &p, direct_store);
   if (rc) return rc > 0 ? 0 : rc;
   const BwdKnobs knobs = dkv_knobs();
   p.head_major = knobs.head_major;
@@ -1224,34 +1285,40 @@ static int launch_bwd_dkv(const magi_ffa_bwd_args* a) {
     grid = cap_grid(grid, a->cu_margin & 0xFFFF, W == 4 ? 2 : 1);
   hipStream_t s = (hipStream_t)a->stream;
   const bool sc = a->softcap > 0.f;
-  if (a->d == 64) launch_dkv<ET, 64, MODE>(W, sc, grid, s, p);
-  else if (a->d == 192) {
-    if constexpr (MODE != 0) launch_dkv<ET, 192, MODE>(W, sc, grid, s, p);
-    else return -6;  // fused + D=192 exceeds LDS; host routes to the split
-  } else launch_dkv<ET, 128, MODE>(W, sc, grid, s, p);
+  // fused + D=192 exceeds LDS; the host routes that head dim to the split
+  if (MODE == 0 && a->d == 192) return -6;
+  auto go = [&](auto direct) {
+    constexpr bool DIRECT = decltype(direct)::value;
+    if (a->d == 64) launch_dkv<ET, 64, MODE, DIRECT>(W, sc, grid, s, p);
+    else if (a->d == 192) {
+      if constexpr (MODE != 0)
+        launch_dkv<ET, 192, MODE, DIRECT>(W, sc, grid, s, p);
+    } else launch_dkv<ET, 128, MODE, DIRECT>(W, sc, grid, s, p);
+  };
+  if (direct_store) go(std::true_type{}); else go(std::false_type{});
   return (int)hipGetLastError();
 }
 
-template <class ET> static int bwd_dkv(const magi_ffa_bwd_args* a) {
-  return launch_bwd_dkv<ET, 0>(a);
+template <class ET> static int bwd_dkv(const magi_ffa_bwd_args* a, bool direct) {
+  return launch_bwd_dkv<ET, 0>(a, direct);
 }
-template <class ET> static int bwd_dv(const magi_ffa_bwd_args* a) {
-  return launch_bwd_dkv<ET, 1>(a);
+template <class ET> static int bwd_dv(const magi_ffa_bwd_args* a, bool direct) {
+  return launch_bwd_dkv<ET, 1>(a, direct);
 }
-template <class ET> static int bwd_dk(const magi_ffa_bwd_args* a) {
-  return launch_bwd_dkv<ET, 2>(a);
+template <class ET> static int bwd_dk(const magi_ffa_bwd_args* a, bool direct) {
+  return launch_bwd_dkv<ET, 2>(a, direct);
 }
 
 extern "C" int magi_ffa_bwd_dkv(const magi_ffa_bwd_args* a) {
-  return BY_ELEM_TYPE(a, bwd_dkv);
+  return BY_ELEM_TYPE(a, bwd_dkv, false);
 }
 
 extern "C" int magi_ffa_bwd_dv(const magi_ffa_bwd_args* a) {
-  return BY_ELEM_TYPE(a, bwd_dv);
+  return BY_ELEM_TYPE(a, bwd_dv, false);
 }
 
 extern "C" int magi_ffa_bwd_dk(const magi_ffa_bwd_args* a) {
-  return BY_ELEM_TYPE(a, bwd_dk);
+  return BY_ELEM_TYPE(a, bwd_dk, false);
 }
 
 extern "C" int magi_ffa_bwd(const magi_ffa_bwd_args* a) {
@@ -1259,4 +1326,30 @@ extern "C" int magi_ffa_bwd(const magi_ffa_bwd_args* a) {
   int rc = magi_ffa_bwd_dq(a);
   if (rc) return rc;
   return magi_ffa_bwd_dkv(a);
+}
+
+// The same passes with the epilogue chosen per pass by the two members behind
+// the embedded struct (magi_ffa.h); a null d is the null-pointer code.
+extern "C" int magi_ffa_bwd_dq_direct(const magi_ffa_bwd_direct_args* d) {
+  if (!d) return -1;
+  return BY_ELEM_TYPE(&d->args, bwd_dq, d->dq_is_16bit != 0);
+}
+
+extern "C" int magi_ffa_bwd_dkv_direct(const magi_ffa_bwd_direct_args* d) {
+  if (!d) return -1;
+  return BY_ELEM_TYPE(&d->args, bwd_dkv, d->dkv_is_16bit != 0);
+}
+
+extern "C" int magi_ffa_bwd_dv_direct(const magi_ffa_bwd_direct_args* d) {
+  if (!d) return -1;
+  return BY_ELEM_TYPE(&d->args, bwd_dv, d->dkv_is_16bit != 0);
+}
+
+extern "C" int magi_ffa_bwd_dk_direct(const magi_ffa_bwd_direct_args* d) {
+  if (!d) return -1;
+  return BY_ELEM_TYPE(&d->args, bwd_dk, d->dkv_is_16bit != 0);
+}
+
+extern "C" int magi_ffa_bwd_direct_args_size(void) {
+  return (int)sizeof(magi_ffa_bwd_direct_args);
 }

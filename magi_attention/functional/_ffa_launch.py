@@ -173,14 +173,27 @@ def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
 def bwd_args(dout, out, dpsum, *, q=None, k=None, v=None, lse=None,
              dq=None, dk=None, dv=None, q_ranges=None, k_ranges=None,
              attn_type_map=None, max_seqlen_k=0, softmax_scale=0.0,
-             softcap=0.0, sm_margin=0) -> _ffa_lib.MagiFfaBwdArgs:
+             softcap=0.0, sm_margin=0) -> _ffa_lib.MagiFfaBwdDirectArgs:
     """The backward argument struct. (dout, out, dpsum) are all the dpsum
     preprocess reads; the dq/dk/dv passes need every member. The tensors must
     be contiguous and outlive the launches. dout's dtype (bf16 or fp16) is the
-    element type of q/k/v too, and of a 16-bit out."""
+    element type of q/k/v too, and of a 16-bit out. The struct is the one of
+    the magi_ffa_bwd_*_direct entries (it passes as the plain one too); the
+    dtypes of dq and of dk/dv pick each pass's epilogue there: f32 = atomic
+    accumulation, the element type = direct store (the caller vouches for
+    disjoint ranges)."""
     tq, hq, d = dout.shape
     tk, hk = (0, 0) if k is None else k.shape[:2]
-    return _ffa_lib.MagiFfaBwdArgs(
+
+    def is_16bit(*grads):
+        dtypes = {g.dtype for g in grads if g is not None}
+        assert len(dtypes) <= 1, f"dk and dv must share a dtype, got {dtypes}"
+        assert dtypes <= {torch.float32, dout.dtype}, (
+            f"gradient buffers are float32 or {dout.dtype}, got {dtypes}"
+        )
+        return int(bool(dtypes) and torch.float32 not in dtypes)
+
+    return _ffa_lib.MagiFfaBwdDirectArgs(
         dout=ptr(dout), q=ptr(q), k=ptr(k), v=ptr(v), out=ptr(out),
         lse=ptr(lse), dq=ptr(dq), dk=ptr(dk), dv=ptr(dv), dpsum=ptr(dpsum),
         q_ranges=ptr(q_ranges), k_ranges=ptr(k_ranges),
@@ -191,6 +204,7 @@ def bwd_args(dout, out, dpsum, *, q=None, k=None, v=None, lse=None,
         softmax_scale=softmax_scale, softcap=softcap,
         cu_margin=sm_margin, stream=current_stream_ptr(),
         elem_type=_ffa_lib.elem_type_of(dout.dtype),
+        dq_is_16bit=is_16bit(dq), dkv_is_16bit=is_16bit(dk, dv),
     )
 
 
@@ -207,22 +221,32 @@ def bwd_dpsum(dout, out) -> torch.Tensor:
     return dpsum
 
 
+def _bwd_entries(args) -> tuple:
+    """The (dq, dkv, dv, dk) entries that take args: the *_direct ones for the
+    struct bwd_args() builds, the plain f32 ones for a bare MagiFfaBwdArgs
+    (the stand-alone probes under tests/ fill one by hand)."""
+    lib = _ffa_lib.lib()
+    sfx = "_direct" if isinstance(args, _ffa_lib.MagiFfaBwdDirectArgs) else ""
+    return tuple(getattr(lib, f"magi_ffa_bwd_{n}{sfx}")
+                 for n in ("dq", "dkv", "dv", "dk"))
+
+
 def run_bwd_deterministic(args, q_ranges, k_ranges, attn_type_map) -> None:
     """Deterministic backward: sequential launches over q-disjoint groups
     (dq pass), k-disjoint groups x GQA head sub-launches (dkv pass) — every
     accumulator element receives its additions in a fixed, stream-ordered
     sequence."""
-    lib = _ffa_lib.lib()
+    bwd_dq, bwd_dkv, bwd_dv, bwd_dk = _bwd_entries(args)
     q_groups = _color_ranges(q_ranges.cpu().tolist())
     k_groups = _color_ranges(k_ranges.cpu().tolist())
     hs = max(args.hq // args.hk, 1)
     if env.is_bwd_split_dkv(args.max_seqlen_k, args.d):
-        dkv = [(lib.magi_ffa_bwd_dv, "bwd_dv[det]", k_groups, hs),
-               (lib.magi_ffa_bwd_dk, "bwd_dk[det]", k_groups, hs)]
+        dkv = [(bwd_dv, "bwd_dv[det]", k_groups, hs),
+               (bwd_dk, "bwd_dk[det]", k_groups, hs)]
     else:
-        dkv = [(lib.magi_ffa_bwd_dkv, "bwd_dkv[det]", k_groups, hs)]
+        dkv = [(bwd_dkv, "bwd_dkv[det]", k_groups, hs)]
     launch_per_group(args, q_ranges, k_ranges, attn_type_map,
-                     [(lib.magi_ffa_bwd_dq, "bwd_dq[det]", q_groups, 1)] + dkv)
+                     [(bwd_dq, "bwd_dq[det]", q_groups, 1)] + dkv)
 
 
 def run_bwd_passes(args, device, dq_tables=None, dkv_tables=None) -> None:
@@ -231,7 +255,7 @@ def run_bwd_passes(args, device, dq_tables=None, dkv_tables=None) -> None:
     co-schedule across the chip. dq_tables / dkv_tables override the range
     tables per pass for auto_range_merge: (ranges_outer, ranges_inner,
     attn_type_map, seg_starts) — outer = the pass's OWN loop dim."""
-    lib = _ffa_lib.lib()
+    bwd_dq, bwd_dkv, bwd_dv, bwd_dk = _bwd_entries(args)
     main = torch.cuda.current_stream(device)
     cosched = env.is_bwd_cosched()
     side = _get_side_stream(device) if cosched else main
@@ -250,14 +274,14 @@ def run_bwd_passes(args, device, dq_tables=None, dkv_tables=None) -> None:
 
     args.stream = ctypes.c_void_p(side.cuda_stream)
     set_tables(dq_tables, True)
-    check(lib.magi_ffa_bwd_dq(args), "magi_ffa_bwd_dq")
+    check(bwd_dq(args), "magi_ffa_bwd_dq")
     args.stream = ctypes.c_void_p(main.cuda_stream)
     set_tables(dkv_tables, False)
     if env.is_bwd_split_dkv(args.max_seqlen_k, args.d):
-        check(lib.magi_ffa_bwd_dv(args), "magi_ffa_bwd_dv")
-        check(lib.magi_ffa_bwd_dk(args), "magi_ffa_bwd_dk")
+        check(bwd_dv(args), "magi_ffa_bwd_dv")
+        check(bwd_dk(args), "magi_ffa_bwd_dk")
     else:
-        check(lib.magi_ffa_bwd_dkv(args), "magi_ffa_bwd_dkv")
+        check(bwd_dkv(args), "magi_ffa_bwd_dkv")
     if cosched:
         main.wait_stream(side)
 

@@ -462,23 +462,81 @@ def _flex_flash_attn_backward(
     sm_margin: int,
     max_seqlen_k: Optional[int] = None,
     auto_range_merge: bool = False,
+    disable_bwd_dq_atomic_reduction: bool = False,
     **_unused,
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """Dense (range-table) backward; returns (dq, dk, dv, dsink). q/k/v are
+    all bf16 or all fp16 (the autograd function upcasts fp8 before it calls).
+
+    By default dq, dk and dv are zeroed f32 buffers that the kernels add
+    their register tiles into with atomics, because ranges may overlap and
+    the q heads of a GQA group share dK/dV rows.
+
+    disable_bwd_dkv_atomic_reduction (reference flex_flash_attn.py:516,
+    :642-647) is the caller's promise that the k ranges are disjoint - under
+    auto_range_merge, the distinct ones, since duplicates merge into one
+    owner. With hq == hk every dK/dV element then has one owner: dk and dv
+    are zero-initialised in dk_type / dv_type, by default k.dtype, stored once
+    by the kernel with no atomics, and returned in that dtype. The stored
+    value is the f32 path's value cast to 16 bit (the same bits, but for a
+    -0 where the f32 path, which adds no zeros, leaves +0). With GQA
+    (hq != hk; the reference allows the flag for MHA or catGQA only) several
+    q heads still add into one row, so the flag falls back to the f32 atomic
+    path and f32 comes back.
+
+    disable_bwd_dq_atomic_reduction is the same for dq and disjoint q ranges
+    (dq_type, default q.dtype). The reference has no such flag, its dQ is not
+    single-owner; here each wave owns its q tile for the whole k loop.
+
+    dq_type / dk_type / dv_type are None, float32 (atomic path whatever the
+    flag says) or q's own 16-bit type, which needs the matching flag (and
+    hq == hk for dk/dv); dk and dv share one dtype. Buffers passed in as dq /
+    dk / dv are zeroed by the caller, follow the same rules by their dtype and
+    are returned as they are. Neither promise is checked, as in the forward:
+    that would take a device sync. With overlapping ranges a direct store
+    loses all but one contribution.
+
+    The context-parallel runtime (dist_attn.py) keeps f32 partial gradients,
+    which it reduces across ranks, and does not use the direct stores."""
     dout, q, k, v, out, q_ranges, k_ranges, attn_type_map = map(
         maybe_contiguous, (dout, q, k, v, out, q_ranges, k_ranges, attn_type_map)
     )
     tq, hq, _ = q.shape
+    hk = k.shape[1]
     # the kernels read dout, and a 16-bit out, as q's element type
     assert q.dtype in (torch.bfloat16, torch.float16)
     assert k.dtype == q.dtype and v.dtype == q.dtype
     assert out.dtype in (torch.float32, q.dtype)
     dout = dout.to(q.dtype)
 
-    # fp32 accumulators, atomically reduced by the kernel
-    dq = torch.zeros_like(q, dtype=torch.float32) if dq is None else dq
-    dk = torch.zeros_like(k, dtype=torch.float32) if dk is None else dk
-    dv = torch.zeros_like(v, dtype=torch.float32) if dv is None else dv
-    assert dq.dtype == dk.dtype == dv.dtype == torch.float32
+    direct_dq = bool(disable_bwd_dq_atomic_reduction)
+    direct_dkv = bool(disable_bwd_dkv_atomic_reduction) and hq == hk
+
+    def grad_buffer(what, like, buf, want, direct, flag):
+        """zeroed f32 accumulator, or 16-bit direct-store target"""
+        dtype = buf.dtype if buf is not None else want or (
+            q.dtype if direct else torch.float32
+        )
+        assert dtype in (torch.float32, q.dtype), (
+            f"{what} {dtype} must be float32 or q's own 16-bit type, "
+            f"q={q.dtype}"
+        )
+        assert dtype == torch.float32 or direct, (
+            f"a 16-bit {what} ({dtype}) is stored directly and needs {flag}"
+        )
+        if buf is None:
+            buf = torch.zeros_like(like, dtype=dtype)
+        return buf
+
+    dkv_flag = (f"disable_bwd_dkv_atomic_reduction with hq == hk "
+                f"(hq={hq}, hk={hk})")
+    dq = grad_buffer("dq", q, dq, dq_type, direct_dq,
+                     "disable_bwd_dq_atomic_reduction")
+    dk = grad_buffer("dk", k, dk, dk_type, direct_dkv, dkv_flag)
+    dv = grad_buffer("dv", v, dv, dv_type, direct_dkv, dkv_flag)
+    assert dk.dtype == dv.dtype, (
+        f"dk and dv share one epilogue: dk={dk.dtype}, dv={dv.dtype}"
+    )
     dpsum = torch.empty(tq, hq, dtype=torch.float32, device=q.device)
 
     if max_seqlen_k is None:
@@ -569,6 +627,10 @@ class FlexFlashAttnFunc(torch.autograd.Function):
         ctx.sm_margin = sm_margin
         ctx.sink_layout = sink_layout
         ctx.auto_range_merge = auto_range_merge
+        # the caller's two promises of disjoint ranges: the forward flag says
+        # the q ranges are, which is what a direct dQ store needs as well
+        ctx.disable_bwd_dq_atomic_reduction = disable_fwd_atomic_reduction
+        ctx.disable_bwd_dkv_atomic_reduction = disable_bwd_dkv_atomic_reduction
         # avoid a per-backward device sync to size the bwd grid
         ctx.max_seqlen_k = max_seqlen_k
         if max_logits is not None:
@@ -580,6 +642,9 @@ class FlexFlashAttnFunc(torch.autograd.Function):
         (q, k, v, out, lse, q_ranges, k_ranges, attn_type_map,
          sink) = ctx.saved_tensors
         in_dtype = q.dtype
+        # fp8 gradients are cast f32 -> fp8 once; a direct bf16 store in
+        # between would round twice, so fp8 keeps the f32 accumulators
+        direct_ok = in_dtype != torch.float8_e4m3fn
         q, k, v, out, dout = _ffa_launch.upcast_fp8(q, k, v, out, dout)
         dq, dk, dv, dsink = _flex_flash_attn_backward(
             dout=dout, q=q, k=k, v=v, sink=sink, sink_layout=ctx.sink_layout,
@@ -587,10 +652,13 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             q_ranges=q_ranges, k_ranges=k_ranges, attn_type_map=attn_type_map,
             softmax_scale=ctx.softmax_scale, softcap=ctx.softcap,
             dq_type=None, dk_type=None, dv_type=None,
-            disable_bwd_dkv_atomic_reduction=False,
+            disable_bwd_dkv_atomic_reduction=(
+                direct_ok and ctx.disable_bwd_dkv_atomic_reduction),
             deterministic=ctx.deterministic, sm_margin=ctx.sm_margin,
             max_seqlen_k=ctx.max_seqlen_k,
             auto_range_merge=ctx.auto_range_merge,
+            disable_bwd_dq_atomic_reduction=(
+                direct_ok and ctx.disable_bwd_dq_atomic_reduction),
         )
         if sink is not None and dsink is not None:
             dsink = dsink.to(sink.dtype)
@@ -658,7 +726,24 @@ def flex_flash_attn_func(
     option of the bf16 path applies (padded head dims, sink, softcap,
     deterministic, auto_range_merge, direct store). P and dS are rounded to
     fp16 before their MFMAs and accumulate in fp32. Mixed 16-bit dtypes are
-    rejected; index_attn_indices stays bf16 / fp8 only."""
+    rejected; index_attn_indices stays bf16 / fp8 only.
+
+    Backward stores (range path, bf16 / fp16). By default dq, dk and dv are
+    accumulated with atomics in f32 buffers and cast once at the end.
+    disable_bwd_dkv_atomic_reduction=True is the promise that the k ranges
+    are disjoint (with auto_range_merge: the distinct k ranges); with
+    hq == hk the dK/dV kernels then store their tiles directly in the input
+    dtype - no f32 buffers, no atomics, no cast pass - and the gradients are
+    equal to the default path's element for element (an exact -0 aside, which
+    the default path returns as +0). With GQA (hq != hk) the flag is
+    accepted and the f32 atomic path runs (the reference allows it for MHA or
+    catGQA only). disable_fwd_atomic_reduction=True, the promise that the q
+    ranges are disjoint, makes the dQ kernel store directly in the same way
+    (the reference has no direct dQ). Neither promise is checked; ranges
+    that do overlap lose contributions. fp8 inputs keep f32 accumulators
+    whatever the flags say, and so does the context-parallel runtime, whose
+    partial gradients are reduced across ranks in f32. What the direct
+    stores save is measured in profiles/bwd_direct_store.md."""
     # ── sparse-input validation (mirrors reference :1344-1384) ──
     _has_ranges = q_ranges is not None
     _has_index = index_attn_indices is not None
@@ -762,6 +847,7 @@ def flex_flash_attn_func(
             sink=sink, sink_layout=sink_layout, softmax_scale=softmax_scale,
             softcap=softcap, deterministic=deterministic, sm_margin=sm_margin,
             disable_fwd_atomic_reduction=disable_fwd_atomic_reduction,
+            disable_bwd_dkv_atomic_reduction=disable_bwd_dkv_atomic_reduction,
             max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k,
             auto_range_merge=auto_range_merge,
             return_max_logits=return_max_logits,
