@@ -170,6 +170,41 @@ int magi_ffa_bwd_dv_direct(const magi_ffa_bwd_direct_args* args);
 int magi_ffa_bwd_dk_direct(const magi_ffa_bwd_direct_args* args);
 int magi_ffa_bwd_direct_args_size(void);
 
+/* cat_gqa (reference flex_flash_attn_func cat_gqa: "concatenate the Q heads
+ * sharing one KV head to optimise the backward under GQA"). magi_ffa_bwd_dkv,
+ * _dv and _dk run one workgroup per (k range, q head, k block), so under GQA
+ * the hq / hk heads of a group each stage the same K/V tiles and all add into
+ * the same dK/dV rows. The entries below take the direct struct embedded
+ * first (a pointer to the new one passes to the older entries) and one more
+ * switch:
+ *   cat_gqa   0: exactly the _direct entry of the same pass, its codes -11
+ *             and -12 included; reserved is not read.
+ *             1: one workgroup per (k range, KV head, k block). It stages its
+ *             K/V tiles once, walks the hq / hk q heads of its group - q
+ *             segments in table order, within a segment q heads ascending -
+ *             into one register tile, and runs the epilogue once. With
+ *             disjoint k ranges every dK/dV element then has a single owner
+ *             for any hq % hk == 0, so dkv_is_16bit is accepted with
+ *             hq != hk. With hq == hk this is the cat_gqa = 0 launch.
+ *   reserved  must be 0.
+ * Validation with cat_gqa = 1, in this order, all before any HIP call: -1,
+ * -2, -3, -9 as above; with dkv_is_16bit set, -12 as above (-11 does not
+ * apply); then -13 a deterministic GQA head split packed into cu_margin's top
+ * 16 bits (the split launches each q head of a group on its own, cat_gqa
+ * walks them in one workgroup: one or the other); -14 reserved != 0; then
+ * n_ranges <= 0 returns 0 without a launch. The dq pass has no cat form: use
+ * magi_ffa_bwd_dq_direct on &args->direct. */
+typedef struct magi_ffa_bwd_cat_args {
+  magi_ffa_bwd_direct_args direct;
+  int32_t cat_gqa;
+  int32_t reserved;
+} magi_ffa_bwd_cat_args;
+
+int magi_ffa_bwd_dkv_cat(const magi_ffa_bwd_cat_args* args);
+int magi_ffa_bwd_dv_cat(const magi_ffa_bwd_cat_args* args);
+int magi_ffa_bwd_dk_cat(const magi_ffa_bwd_cat_args* args);
+int magi_ffa_bwd_cat_args_size(void);
+
 /* ------------------------------------------------------------------ *
  * Range row ops (reference common/range_op/_range_*.py — Triton there,
  * hand-written HIP here; pack/unpack engine of the group collectives). *

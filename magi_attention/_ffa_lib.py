@@ -103,6 +103,19 @@ class MagiFfaBwdDirectArgs(MagiFfaBwdArgs):
     ]
 
 
+class MagiFfaBwdCatArgs(MagiFfaBwdDirectArgs):
+    """mirrors magi_ffa_bwd_cat_args: magi_ffa_bwd_direct_args embedded first,
+    then the cat_gqa switch of the magi_ffa_bwd_*_cat entries. An instance
+    also passes as the two structs it starts with."""
+
+    _fields_ = [
+        # 1: a dK/dV workgroup owns a KV head and walks the q heads of its
+        # group; 0: one workgroup per q head, the _direct entries' launch
+        ("cat_gqa", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),  # must be 0
+    ]
+
+
 class MagiRangeOpArgs(ctypes.Structure):
     _fields_ = [
         ("input", ctypes.c_void_p),
@@ -263,6 +276,10 @@ def _try_load() -> ctypes.CDLL | None:
             ("magi_ffa_bwd_dv_direct", [ctypes.POINTER(MagiFfaBwdDirectArgs)]),
             ("magi_ffa_bwd_dk_direct", [ctypes.POINTER(MagiFfaBwdDirectArgs)]),
             ("magi_ffa_bwd_direct_args_size", []),
+            ("magi_ffa_bwd_dkv_cat", [ctypes.POINTER(MagiFfaBwdCatArgs)]),
+            ("magi_ffa_bwd_dv_cat", [ctypes.POINTER(MagiFfaBwdCatArgs)]),
+            ("magi_ffa_bwd_dk_cat", [ctypes.POINTER(MagiFfaBwdCatArgs)]),
+            ("magi_ffa_bwd_cat_args_size", []),
             ("magi_range_gather", [ctypes.POINTER(MagiRangeOpArgs)]),
             ("magi_range_reduce", [ctypes.POINTER(MagiRangeOpArgs)]),
             ("magi_correct_out_lse", [ctypes.POINTER(MagiCorrectArgs)]),
@@ -293,6 +310,17 @@ def _try_load() -> ctypes.CDLL | None:
         lib.magi_ffa_abi_version.restype = ctypes.c_int
         lib.magi_ffa_args_size.argtypes = [ctypes.c_int]
         lib.magi_ffa_args_size.restype = ctypes.c_int
+        # a mirror of another size than the struct as compiled would make a
+        # kernel read garbage pointers
+        for cls, size in [
+            (MagiFfaBwdDirectArgs, lib.magi_ffa_bwd_direct_args_size()),
+            (MagiFfaBwdCatArgs, lib.magi_ffa_bwd_cat_args_size()),
+        ]:
+            if ctypes.sizeof(cls) != size:
+                raise RuntimeError(
+                    f"{cls.__name__} is {ctypes.sizeof(cls)} bytes, the "
+                    f"library at {_LIB_PATH} was compiled with {size}: rebuild"
+                )
         _lib = lib
     except OSError as e:  # missing .so or missing HIP runtime
         _load_error = e

@@ -78,6 +78,9 @@ struct BwdParams {
   int hq, hk, gqa;
   float scale;
   float softcap;
+  int cat;           // q heads one dkv workgroup walks: 1, or gqa (cat_gqa);
+                     // here it takes the padding in front of total_q and
+                     // moves no other member
   long long total_q, total_k;
   int head_major;    // 1: blockIdx.x = head (XCD-affine); 0: work-major
   int work_nx, work_ny, work_nz;  // flattened work space (strided-grid mode)
@@ -135,7 +138,18 @@ __global__ __launch_bounds__(256) void bwd_preprocess_kernel(BwdParams<ET> p,
 // 3-ring exceed the 160 KB LDS), and so do 4-wave workgroups (3 buffers
 // exceed the 80 KB/WG budget of 2 blocks/CU).
 // DIRECT: the epilogue (see the head of the file); nothing before it differs.
-template <class ET, int D, bool HAS_SOFTCAP, int MODE, int WAVES, bool DIRECT>
+// CAT (cat_gqa): the head index of a work item is the KV head, and the
+// workgroup walks the p.cat = gqa q heads h = kh * gqa + j of that group into
+// the one dK/dV register tile, so K/V are staged once per group and every
+// dK/dV row has one owner per k range. Visiting order, a function of the
+// tables alone: q segments in order, and within a segment j ascending. Each
+// (segment, head) pass is a whole pass of the segment loop: fresh ring state
+// and prologue stages, the segment's closing barrier, nothing staged or
+// prefetched carried from one head to the next. CAT is a template parameter,
+// not a runtime p.cat, so that the CAT = false kernels stay the code they
+// were (profiles/bwd_cat_gqa.md has both resource tables).
+template <class ET, int D, bool HAS_SOFTCAP, int MODE, int WAVES, bool DIRECT,
+          bool CAT>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 8 ? 2 : 1)
 void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
   using Tr = ElemTraits<ET>;
@@ -182,7 +196,9 @@ void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
   const int wz = (int)(w2 / p.work_ny);
   const int ri = wz;
   const int hidx = p.head_major ? wx : wy;
-  const int h = p.head_off + hidx * p.head_mult;
+  // CAT: the kv head; the q head h is set per pass of the segment loop
+  const int hsel = p.head_off + hidx * p.head_mult;
+  int h = CAT ? hsel * p.gqa : hsel;
   const int wb = p.head_major ? wy : wx;
   const int ks = p.k_ranges[2 * ri], ke = p.k_ranges[2 * ri + 1];
   const int nblk0 = ks + wb * (BWD_BN * WAVES);
@@ -210,7 +226,7 @@ void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
   const float cap_pre = HAS_SOFTCAP ? p.scale / p.softcap : 0.f;
   const float log2e = 1.4426950408889634f;
 
-  const int kh = h / p.gqa;
+  const int kh = CAT ? hsel : h / p.gqa;
   const size_t k_pitch = (size_t)p.hk * D;
   const size_t q_pitch = (size_t)p.hq * D;
 
@@ -339,6 +355,7 @@ void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
   constexpr int GLDS_PER_WAVE =
       (GLDS_TOTAL % WAVES == 0) ? GLDS_TOTAL / WAVES : 0;  // 0 = non-uniform
   // block-uniform operands of the staging addresses (scalar registers)
+  // (CAT: re-pointed at each head of the group by the segment loop)
   const ET* q_head = p.q + (size_t)h * D;
   const ET* do_head = p.dout + (size_t)h * D;
   const int smem_byte = (int)(unsigned long long)(
@@ -424,13 +441,21 @@ void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
     }
   };
   int cur = 0;
-  for (int seg = seg0; seg < seg1; ++seg) {
+  // CAT folds (segment, head of the group) into this one loop: j counts the
+  // heads of the current segment and seg moves on when j wraps
+  for (int seg = seg0, j = 0; seg < seg1;
+       (CAT && ++j < p.cat) ? 0 : (j = 0, ++seg)) {
   qs = p.q_ranges[2 * seg];
   qe = p.q_ranges[2 * seg + 1];
   atype = p.attn_type_map ? p.attn_type_map[seg] : 0;
   if (qe <= qs) continue;  // uniform across block
   seg_bounds();
   if (q_lo >= q_hi) continue;
+  if constexpr (CAT) {
+    h = kh * p.gqa + j;
+    q_head = p.q + (size_t)h * D;
+    do_head = p.dout + (size_t)h * D;
+  }
   cur = 0;
   if constexpr (V_IN_LDS) load_lsedp(q_lo);
   stage_glds(0, q_lo);
@@ -670,8 +695,8 @@ void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
   // ---- write dK/dV ----
   if (wave_live) {
   if constexpr (DIRECT) {
-    // single owner (disjoint k ranges, hq == hk): the rounded tile IS the
-    // row, zeros included - the number the atomic add into a zeroed f32
+    // single owner (disjoint k ranges; hq == hk, or CAT): the rounded tile
+    // IS the row, zeros included - the number the atomic add into a zeroed f32
     // buffer followed by a cast gives. from_f32 rounds the finished f32
     // value. pin_vgpr on the dK tile in front of each row's converts changes
     // no value; it steers the register allocator: without it the 8-wave
@@ -1097,25 +1122,39 @@ extern "C" int magi_ffa_bwd_preprocess(const magi_ffa_bwd_args* a) {
   return BY_ELEM_TYPE(a, bwd_preprocess);
 }
 
+// What the _direct and _cat entries add to a dkv pass over magi_ffa_bwd_args
+struct DkvOpts {
+  bool direct;   // dkv_is_16bit: the direct-store epilogue
+  bool cat;      // cat_gqa: one workgroup walks the q heads of a kv head
+  int reserved;  // magi_ffa_bwd_cat_args.reserved, 0 from the other entries
+};
+
 // Validation shared by the dq and dkv entries, in the order magi_ffa.h
-// documents; no HIP call before it. dkv_direct adds the rules of the direct
-// dK/dV store, which has no other head or launch adding into its rows.
-static int check_bwd_args(const magi_ffa_bwd_args* a, bool dkv_direct) {
+// documents; no HIP call before it. o.direct adds the rules of the direct
+// dK/dV store, which has no other head or launch adding into its rows: that
+// is hq == hk, or cat_gqa, whose workgroup is the only one of its kv head.
+static int check_bwd_args(const magi_ffa_bwd_args* a, const DkvOpts& o) {
   if (!a || !a->dout || !a->q || !a->k || !a->v || !a->lse) return -1;
   if (a->d != 64 && a->d != 128 && a->d != 192) return -2;
   if (a->hq % a->hk != 0) return -3;
   if (!elem_type_known(a->elem_type)) return -9;
-  if (dkv_direct) {
-    if (a->hq != a->hk) return -11;
+  if (o.direct) {
+    if (a->hq != a->hk && !o.cat) return -11;
     if (a->cu_margin & 0xFFFF0000) return -12;
+  }
+  if (o.cat) {
+    // the head split gives each q head of a group a launch of its own;
+    // cat_gqa walks them in one workgroup
+    if (a->cu_margin & 0xFFFF0000) return -13;
+    if (o.reserved != 0) return -14;
   }
   return 0;
 }
 
 template <class ET>
 static int fill_bwd_params(const magi_ffa_bwd_args* a, BwdParams<ET>* p,
-                           bool dkv_direct) {
-  if (const int rc = check_bwd_args(a, dkv_direct)) return rc;
+                           const DkvOpts& o) {
+  if (const int rc = check_bwd_args(a, o)) return rc;
   if (a->n_ranges <= 0) return 1;  // caller treats >0 as "nothing to do"
   p->dout = (const ET*)a->dout;
   p->q = (const ET*)a->q;
@@ -1133,6 +1172,8 @@ static int fill_bwd_params(const magi_ffa_bwd_args* a, BwdParams<ET>* p,
   p->hq = a->hq;
   p->hk = a->hk;
   p->gqa = a->hq / a->hk;
+  // cat_gqa over a group of one head is the plain kernel
+  p->cat = (o.cat && p->gqa > 1) ? p->gqa : 1;
   p->scale = a->softmax_scale;
   p->softcap = a->softcap;
   p->total_q = a->total_q;
@@ -1148,6 +1189,7 @@ static int fill_bwd_params(const magi_ffa_bwd_args* a, BwdParams<ET>* p,
     p->head_off = (a->cu_margin >> 16) & 0xFF;
     p->n_heads_launch = a->hq / p->head_mult;
   }
+  if (p->cat > 1) p->n_heads_launch = a->hk;  // the head index is the kv head
   return 0;
 }
 
@@ -1208,7 +1250,7 @@ static void launch_dq(int waves, bool sc, dim3 grid, hipStream_t s,
 template <class ET>
 static int bwd_dq(const magi_ffa_bwd_args* a, bool direct_store) {
   BwdParams<ET> p;
-  int rc = fill_bwd_params(a, &p, false);
+  int rc = fill_bwd_params(a, &p, DkvOpts{false, false, 0});
   if (rc) return rc > 0 ? 0 : rc;
   const BwdKnobs knobs = dq_knobs(a);
   p.head_major = knobs.head_major;
@@ -1249,12 +1291,12 @@ static BwdKnobs dkv_knobs() {
   return {env_int("MAGI_BWD_HEAD_MAJOR", 1), env_int("MAGI_BWD_BIGSEQ", 1024)};
 }
 
-template <class ET, int D, int MODE, bool DIRECT>
+template <class ET, int D, int MODE, bool DIRECT, bool CAT>
 static void launch_dkv(int waves, bool sc, dim3 grid, hipStream_t s,
                        const BwdParams<ET>& p) {
-#define GO(SC, W)                                                           \
-  hipLaunchKernelGGL((ffa_bwd_dkv_kernel<ET, D, SC, MODE, W, DIRECT>), grid, \
-                     dim3(64 * W), 0, s, p)
+#define GO(SC, W)                                                          \
+  hipLaunchKernelGGL((ffa_bwd_dkv_kernel<ET, D, SC, MODE, W, DIRECT, CAT>), \
+                     grid, dim3(64 * W), 0, s, p)
   if constexpr (D != 192) {  // D=192 spills at 8 waves: 4-wave builds only
     if (waves == 8) {
       if (sc) GO(true, 8); else GO(false, 8);
@@ -1266,9 +1308,9 @@ static void launch_dkv(int waves, bool sc, dim3 grid, hipStream_t s,
 }
 
 template <class ET, int MODE>
-static int launch_bwd_dkv(const magi_ffa_bwd_args* a, bool direct_store) {
+static int launch_bwd_dkv(const magi_ffa_bwd_args* a, const DkvOpts& o) {
   BwdParams<ET> p;
-  int rc = fill_bwd_params(a, &p, direct_store);
+  int rc = fill_bwd_params(a, &p, o);
   if (rc) return rc > 0 ? 0 : rc;
   const BwdKnobs knobs = dkv_knobs();
   p.head_major = knobs.head_major;
@@ -1287,38 +1329,46 @@ static int launch_bwd_dkv(const magi_ffa_bwd_args* a, bool direct_store) {
   const bool sc = a->softcap > 0.f;
   // fused + D=192 exceeds LDS; the host routes that head dim to the split
   if (MODE == 0 && a->d == 192) return -6;
-  auto go = [&](auto direct) {
+  auto go = [&](auto direct, auto cat) {
     constexpr bool DIRECT = decltype(direct)::value;
-    if (a->d == 64) launch_dkv<ET, 64, MODE, DIRECT>(W, sc, grid, s, p);
+    constexpr bool CAT = decltype(cat)::value;
+    if (a->d == 64) launch_dkv<ET, 64, MODE, DIRECT, CAT>(W, sc, grid, s, p);
     else if (a->d == 192) {
       if constexpr (MODE != 0)
-        launch_dkv<ET, 192, MODE, DIRECT>(W, sc, grid, s, p);
-    } else launch_dkv<ET, 128, MODE, DIRECT>(W, sc, grid, s, p);
+        launch_dkv<ET, 192, MODE, DIRECT, CAT>(W, sc, grid, s, p);
+    } else launch_dkv<ET, 128, MODE, DIRECT, CAT>(W, sc, grid, s, p);
   };
-  if (direct_store) go(std::true_type{}); else go(std::false_type{});
+  auto go_cat = [&](auto direct) {
+    if (p.cat > 1) go(direct, std::true_type{});
+    else go(direct, std::false_type{});
+  };
+  if (o.direct) go_cat(std::true_type{}); else go_cat(std::false_type{});
   return (int)hipGetLastError();
 }
 
-template <class ET> static int bwd_dkv(const magi_ffa_bwd_args* a, bool direct) {
-  return launch_bwd_dkv<ET, 0>(a, direct);
+template <class ET>
+static int bwd_dkv(const magi_ffa_bwd_args* a, const DkvOpts& o) {
+  return launch_bwd_dkv<ET, 0>(a, o);
 }
-template <class ET> static int bwd_dv(const magi_ffa_bwd_args* a, bool direct) {
-  return launch_bwd_dkv<ET, 1>(a, direct);
+template <class ET>
+static int bwd_dv(const magi_ffa_bwd_args* a, const DkvOpts& o) {
+  return launch_bwd_dkv<ET, 1>(a, o);
 }
-template <class ET> static int bwd_dk(const magi_ffa_bwd_args* a, bool direct) {
-  return launch_bwd_dkv<ET, 2>(a, direct);
+template <class ET>
+static int bwd_dk(const magi_ffa_bwd_args* a, const DkvOpts& o) {
+  return launch_bwd_dkv<ET, 2>(a, o);
 }
 
 extern "C" int magi_ffa_bwd_dkv(const magi_ffa_bwd_args* a) {
-  return BY_ELEM_TYPE(a, bwd_dkv, false);
+  return BY_ELEM_TYPE(a, bwd_dkv, DkvOpts{false, false, 0});
 }
 
 extern "C" int magi_ffa_bwd_dv(const magi_ffa_bwd_args* a) {
-  return BY_ELEM_TYPE(a, bwd_dv, false);
+  return BY_ELEM_TYPE(a, bwd_dv, DkvOpts{false, false, 0});
 }
 
 extern "C" int magi_ffa_bwd_dk(const magi_ffa_bwd_args* a) {
-  return BY_ELEM_TYPE(a, bwd_dk, false);
+  return BY_ELEM_TYPE(a, bwd_dk, DkvOpts{false, false, 0});
 }
 
 extern "C" int magi_ffa_bwd(const magi_ffa_bwd_args* a) {
@@ -1335,21 +1385,51 @@ extern "C" int magi_ffa_bwd_dq_direct(const magi_ffa_bwd_direct_args* d) {
   return BY_ELEM_TYPE(&d->args, bwd_dq, d->dq_is_16bit != 0);
 }
 
+static DkvOpts direct_opts(const magi_ffa_bwd_direct_args* d) {
+  return DkvOpts{d->dkv_is_16bit != 0, false, 0};
+}
+
 extern "C" int magi_ffa_bwd_dkv_direct(const magi_ffa_bwd_direct_args* d) {
   if (!d) return -1;
-  return BY_ELEM_TYPE(&d->args, bwd_dkv, d->dkv_is_16bit != 0);
+  return BY_ELEM_TYPE(&d->args, bwd_dkv, direct_opts(d));
 }
 
 extern "C" int magi_ffa_bwd_dv_direct(const magi_ffa_bwd_direct_args* d) {
   if (!d) return -1;
-  return BY_ELEM_TYPE(&d->args, bwd_dv, d->dkv_is_16bit != 0);
+  return BY_ELEM_TYPE(&d->args, bwd_dv, direct_opts(d));
 }
 
 extern "C" int magi_ffa_bwd_dk_direct(const magi_ffa_bwd_direct_args* d) {
   if (!d) return -1;
-  return BY_ELEM_TYPE(&d->args, bwd_dk, d->dkv_is_16bit != 0);
+  return BY_ELEM_TYPE(&d->args, bwd_dk, direct_opts(d));
 }
 
 extern "C" int magi_ffa_bwd_direct_args_size(void) {
   return (int)sizeof(magi_ffa_bwd_direct_args);
+}
+
+// The dkv passes once more behind magi_ffa_bwd_cat_args (magi_ffa.h): with
+// cat_gqa == 0 the _direct entries, reserved unread.
+static DkvOpts cat_opts(const magi_ffa_bwd_cat_args* c) {
+  if (!c->cat_gqa) return direct_opts(&c->direct);
+  return DkvOpts{c->direct.dkv_is_16bit != 0, true, c->reserved};
+}
+
+extern "C" int magi_ffa_bwd_dkv_cat(const magi_ffa_bwd_cat_args* c) {
+  if (!c) return -1;
+  return BY_ELEM_TYPE(&c->direct.args, bwd_dkv, cat_opts(c));
+}
+
+extern "C" int magi_ffa_bwd_dv_cat(const magi_ffa_bwd_cat_args* c) {
+  if (!c) return -1;
+  return BY_ELEM_TYPE(&c->direct.args, bwd_dv, cat_opts(c));
+}
+
+extern "C" int magi_ffa_bwd_dk_cat(const magi_ffa_bwd_cat_args* c) {
+  if (!c) return -1;
+  return BY_ELEM_TYPE(&c->direct.args, bwd_dk, cat_opts(c));
+}
+
+extern "C" int magi_ffa_bwd_cat_args_size(void) {
+  return (int)sizeof(magi_ffa_bwd_cat_args);
 }

@@ -46,8 +46,13 @@ def is_profile_mode_enable() -> bool:
 
 
 def is_cat_gqa_enable() -> bool:
-    """Reference: concatenate GQA heads for wider SM90 tiles. No MI355X
-    analogue (the wave64 tiling covers heads directly); accepted, unused."""
+    """Reference: concatenate the Q heads sharing one KV head in the backward
+    under GQA. Here (MAGI_ATTENTION_CATGQA=1, off by default) the context-
+    parallel runtime passes cat_gqa=True to its dK/dV launches: a workgroup
+    owns a KV head and walks the q heads of its group into one register tile,
+    so K/V are staged once per group, the f32 partial dK/dV get one atomic add
+    per KV head, and deterministic mode needs no per-head sub-launches. The
+    single-GPU flex_flash_attn_func takes its own cat_gqa argument."""
     return _get_bool("MAGI_ATTENTION_CATGQA")
 
 

@@ -173,15 +173,17 @@ def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
 def bwd_args(dout, out, dpsum, *, q=None, k=None, v=None, lse=None,
              dq=None, dk=None, dv=None, q_ranges=None, k_ranges=None,
              attn_type_map=None, max_seqlen_k=0, softmax_scale=0.0,
-             softcap=0.0, sm_margin=0) -> _ffa_lib.MagiFfaBwdDirectArgs:
+             softcap=0.0, sm_margin=0,
+             cat_gqa=False) -> _ffa_lib.MagiFfaBwdCatArgs:
     """The backward argument struct. (dout, out, dpsum) are all the dpsum
     preprocess reads; the dq/dk/dv passes need every member. The tensors must
     be contiguous and outlive the launches. dout's dtype (bf16 or fp16) is the
     element type of q/k/v too, and of a 16-bit out. The struct is the one of
-    the magi_ffa_bwd_*_direct entries (it passes as the plain one too); the
-    dtypes of dq and of dk/dv pick each pass's epilogue there: f32 = atomic
-    accumulation, the element type = direct store (the caller vouches for
-    disjoint ranges)."""
+    the magi_ffa_bwd_*_cat entries (it passes as the _direct and the plain one
+    too); the dtypes of dq and of dk/dv pick each pass's epilogue there: f32 =
+    atomic accumulation, the element type = direct store (the caller vouches
+    for disjoint ranges). cat_gqa: a dK/dV workgroup owns a KV head and walks
+    the q heads of its group, so each dK/dV row of a k range has one owner."""
     tq, hq, d = dout.shape
     tk, hk = (0, 0) if k is None else k.shape[:2]
 
@@ -193,7 +195,7 @@ def bwd_args(dout, out, dpsum, *, q=None, k=None, v=None, lse=None,
         )
         return int(bool(dtypes) and torch.float32 not in dtypes)
 
-    return _ffa_lib.MagiFfaBwdDirectArgs(
+    return _ffa_lib.MagiFfaBwdCatArgs(
         dout=ptr(dout), q=ptr(q), k=ptr(k), v=ptr(v), out=ptr(out),
         lse=ptr(lse), dq=ptr(dq), dk=ptr(dk), dv=ptr(dv), dpsum=ptr(dpsum),
         q_ranges=ptr(q_ranges), k_ranges=ptr(k_ranges),
@@ -205,6 +207,7 @@ def bwd_args(dout, out, dpsum, *, q=None, k=None, v=None, lse=None,
         cu_margin=sm_margin, stream=current_stream_ptr(),
         elem_type=_ffa_lib.elem_type_of(dout.dtype),
         dq_is_16bit=is_16bit(dq), dkv_is_16bit=is_16bit(dk, dv),
+        cat_gqa=int(bool(cat_gqa)),
     )
 
 
@@ -222,24 +225,28 @@ def bwd_dpsum(dout, out) -> torch.Tensor:
 
 
 def _bwd_entries(args) -> tuple:
-    """The (dq, dkv, dv, dk) entries that take args: the *_direct ones for the
-    struct bwd_args() builds, the plain f32 ones for a bare MagiFfaBwdArgs
-    (the stand-alone probes under tests/ fill one by hand)."""
+    """The (dq, dkv, dv, dk) entries that take args: the *_cat ones (dq has
+    none: its *_direct one) for the struct bwd_args() builds, the *_direct
+    ones for a MagiFfaBwdDirectArgs, the plain f32 ones for a bare
+    MagiFfaBwdArgs (the stand-alone probes under tests/ fill one by hand)."""
     lib = _ffa_lib.lib()
     sfx = "_direct" if isinstance(args, _ffa_lib.MagiFfaBwdDirectArgs) else ""
-    return tuple(getattr(lib, f"magi_ffa_bwd_{n}{sfx}")
-                 for n in ("dq", "dkv", "dv", "dk"))
+    dkv_sfx = "_cat" if isinstance(args, _ffa_lib.MagiFfaBwdCatArgs) else sfx
+    return tuple(getattr(lib, f"magi_ffa_bwd_{n}{s}")
+                 for n, s in (("dq", sfx), ("dkv", dkv_sfx), ("dv", dkv_sfx),
+                              ("dk", dkv_sfx)))
 
 
 def run_bwd_deterministic(args, q_ranges, k_ranges, attn_type_map) -> None:
     """Deterministic backward: sequential launches over q-disjoint groups
     (dq pass), k-disjoint groups x GQA head sub-launches (dkv pass) — every
     accumulator element receives its additions in a fixed, stream-ordered
-    sequence."""
+    sequence. Under cat_gqa one workgroup walks the heads of a group in a
+    fixed order, so a k group is one launch whatever hq / hk is."""
     bwd_dq, bwd_dkv, bwd_dv, bwd_dk = _bwd_entries(args)
     q_groups = _color_ranges(q_ranges.cpu().tolist())
     k_groups = _color_ranges(k_ranges.cpu().tolist())
-    hs = max(args.hq // args.hk, 1)
+    hs = 1 if getattr(args, "cat_gqa", 0) else max(args.hq // args.hk, 1)
     if env.is_bwd_split_dkv(args.max_seqlen_k, args.d):
         dkv = [(bwd_dv, "bwd_dv[det]", k_groups, hs),
                (bwd_dk, "bwd_dk[det]", k_groups, hs)]

@@ -397,6 +397,9 @@ class DistAttnRuntime:
             softmax_scale=scale, softcap=softcap,
             sm_margin=(env.ffa_backward_sm_margin()
                        if dist.get_world_size(self.cp_group) > 1 else 0),
+            # dk / dv stay f32 partials here: the gain is one atomic add per
+            # KV head and no GQA sub-launches in deterministic mode
+            cat_gqa=env.general.is_cat_gqa_enable(),
         )
         merged = (arg.to_device_merged(q.device)
                   if env.is_auto_range_merge_enable() and not deterministic

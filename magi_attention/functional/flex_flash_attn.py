@@ -463,6 +463,7 @@ def _flex_flash_attn_backward(
     max_seqlen_k: Optional[int] = None,
     auto_range_merge: bool = False,
     disable_bwd_dq_atomic_reduction: bool = False,
+    cat_gqa: bool = False,
     **_unused,
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """Dense (range-table) backward; returns (dq, dk, dv, dsink). q/k/v are
@@ -481,8 +482,19 @@ def _flex_flash_attn_backward(
     value is the f32 path's value cast to 16 bit (the same bits, but for a
     -0 where the f32 path, which adds no zeros, leaves +0). With GQA
     (hq != hk; the reference allows the flag for MHA or catGQA only) several
-    q heads still add into one row, so the flag falls back to the f32 atomic
-    path and f32 comes back.
+    q heads still add into one row, so without cat_gqa the flag falls back to
+    the f32 atomic path and f32 comes back.
+
+    cat_gqa (reference flex_flash_attn.py:1202) takes effect when hq != hk
+    (with hq == hk it is today's launch): a dK/dV workgroup owns (k range, KV
+    head, k block) in place of (k range, q head, k block), stages its K/V
+    tiles once and walks the hq / hk q heads of its group into one register
+    tile - q segments in table order, heads ascending within a segment. The
+    epilogue runs once per KV head, so disjoint k ranges have one owner per
+    dK/dV element and disable_bwd_dkv_atomic_reduction stores directly under
+    GQA too. It composes with auto_range_merge, deterministic (one launch per
+    k-disjoint group: no per-head sub-launches), the split and the fused dK/dV
+    passes, softcap, sink and padded head dims. The dq pass is not touched.
 
     disable_bwd_dq_atomic_reduction is the same for dq and disjoint q ranges
     (dq_type, default q.dtype). The reference has no such flag, its dQ is not
@@ -490,7 +502,7 @@ def _flex_flash_attn_backward(
 
     dq_type / dk_type / dv_type are None, float32 (atomic path whatever the
     flag says) or q's own 16-bit type, which needs the matching flag (and
-    hq == hk for dk/dv); dk and dv share one dtype. Buffers passed in as dq /
+    hq == hk or cat_gqa for dk/dv); dk and dv share one dtype. Buffers passed in as dq /
     dk / dv are zeroed by the caller, follow the same rules by their dtype and
     are returned as they are. Neither promise is checked, as in the forward:
     that would take a device sync. With overlapping ranges a direct store
@@ -510,7 +522,10 @@ def _flex_flash_attn_backward(
     dout = dout.to(q.dtype)
 
     direct_dq = bool(disable_bwd_dq_atomic_reduction)
-    direct_dkv = bool(disable_bwd_dkv_atomic_reduction) and hq == hk
+    cat_gqa = bool(cat_gqa) and hq != hk
+    direct_dkv = bool(disable_bwd_dkv_atomic_reduction) and (
+        hq == hk or cat_gqa
+    )
 
     def grad_buffer(what, like, buf, want, direct, flag):
         """zeroed f32 accumulator, or 16-bit direct-store target"""
@@ -528,8 +543,10 @@ def _flex_flash_attn_backward(
             buf = torch.zeros_like(like, dtype=dtype)
         return buf
 
-    dkv_flag = (f"disable_bwd_dkv_atomic_reduction with hq == hk "
-                f"(hq={hq}, hk={hk})")
+    dkv_flag = (
+        "disable_bwd_dkv_atomic_reduction" if cat_gqa else
+        f"disable_bwd_dkv_atomic_reduction with hq == hk (hq={hq}, hk={hk})"
+    )
     dq = grad_buffer("dq", q, dq, dq_type, direct_dq,
                      "disable_bwd_dq_atomic_reduction")
     dk = grad_buffer("dk", k, dk, dk_type, direct_dkv, dkv_flag)
@@ -546,7 +563,7 @@ def _flex_flash_attn_backward(
         dout, out, dpsum, q=q, k=k, v=v, lse=lse, dq=dq, dk=dk, dv=dv,
         q_ranges=q_ranges, k_ranges=k_ranges, attn_type_map=attn_type_map,
         max_seqlen_k=max_seqlen_k, softmax_scale=softmax_scale,
-        softcap=softcap, sm_margin=sm_margin,
+        softcap=softcap, sm_margin=sm_margin, cat_gqa=cat_gqa,
     )
     _ffa_launch.bwd_preprocess(args)
     if sink is not None:
@@ -633,6 +650,7 @@ class FlexFlashAttnFunc(torch.autograd.Function):
         ctx.disable_bwd_dkv_atomic_reduction = disable_bwd_dkv_atomic_reduction
         # avoid a per-backward device sync to size the bwd grid
         ctx.max_seqlen_k = max_seqlen_k
+        ctx.cat_gqa = cat_gqa
         if max_logits is not None:
             ctx.mark_non_differentiable(max_logits)
         return out, lse, max_logits
@@ -659,6 +677,7 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             auto_range_merge=ctx.auto_range_merge,
             disable_bwd_dq_atomic_reduction=(
                 direct_ok and ctx.disable_bwd_dq_atomic_reduction),
+            cat_gqa=ctx.cat_gqa,
         )
         if sink is not None and dsink is not None:
             dsink = dsink.to(sink.dtype)
@@ -735,15 +754,24 @@ def flex_flash_attn_func(
     hq == hk the dK/dV kernels then store their tiles directly in the input
     dtype - no f32 buffers, no atomics, no cast pass - and the gradients are
     equal to the default path's element for element (an exact -0 aside, which
-    the default path returns as +0). With GQA (hq != hk) the flag is
-    accepted and the f32 atomic path runs (the reference allows it for MHA or
-    catGQA only). disable_fwd_atomic_reduction=True, the promise that the q
+    the default path returns as +0). With GQA (hq != hk) and no cat_gqa the
+    flag is accepted and the f32 atomic path runs (the reference allows it for
+    MHA or catGQA only). cat_gqa=True (it acts when hq != hk) makes each dK/dV
+    workgroup own a KV head: it stages K/V once and walks the hq / hk q heads
+    of the group into one register tile, in place of hq / hk workgroups that
+    stage the same tiles and add into the same rows. dK/dV then get one add
+    per KV head, deterministic=True needs no per-head sub-launches, and
+    with the dkv flag the direct store runs under GQA as well, equal element
+    for element to the cat_gqa f32 gradients cast to the input dtype. It
+    cannot be combined with pack_gqa; whether it pays is measured in
+    profiles/bwd_cat_gqa.md. disable_fwd_atomic_reduction=True, the promise that the q
     ranges are disjoint, makes the dQ kernel store directly in the same way
     (the reference has no direct dQ). Neither promise is checked; ranges
     that do overlap lose contributions. fp8 inputs keep f32 accumulators
     whatever the flags say, and so does the context-parallel runtime, whose
     partial gradients are reduced across ranks in f32. What the direct
     stores save is measured in profiles/bwd_direct_store.md."""
+    assert not (pack_gqa and cat_gqa), "pack_gqa and cat_gqa cannot be both True"
     # ── sparse-input validation (mirrors reference :1344-1384) ──
     _has_ranges = q_ranges is not None
     _has_index = index_attn_indices is not None
@@ -851,6 +879,7 @@ def flex_flash_attn_func(
             max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k,
             auto_range_merge=auto_range_merge,
             return_max_logits=return_max_logits,
+            pack_gqa=pack_gqa, cat_gqa=cat_gqa,
         )
         return out[..., :d], meta
     out, lse, max_logits = FlexFlashAttnFunc.apply(
