@@ -75,6 +75,48 @@ typedef struct magi_ffa_fwd_args {
  * out. magi_ffa_fwd_fp8 (raw e4m3 q/k/v) ignores elem_type. */
 int magi_ffa_fwd(const magi_ffa_fwd_args* args);
 
+/* pack_gqa (reference flex_flash_attn_func pack_gqa: "pack the Q heads that
+ * share one KV head into one q tile"). magi_ffa_fwd runs one workgroup per
+ * (q range, q head, block of q rows), a wave owning 32 consecutive tokens of
+ * one head: on block-sparse and short-document masks, where q ranges are
+ * short, most of each wave is empty and the hq / hk heads of a group each
+ * stage the same K/V rows. magi_ffa_fwd_args keeps its size and its last
+ * member (bindings check both), so the switch rides behind an embedded copy:
+ *   pack_gqa  0: exactly magi_ffa_fwd(&args), bit for bit; reserved is not
+ *             read.
+ *             1: one workgroup per (q range, KV head, block of packed rows).
+ *             With G = hq / hk (any value, a power of two or not), q range
+ *             [qs, qe) has (qe - qs) * G packed rows; row r is token
+ *             qs + r / G, q head kh * G + r % G. K/V is staged once per
+ *             workgroup for all G heads. out, lse and max_logits have the
+ *             usual layout and meaning; every member of args keeps its
+ *             meaning (qk_starts, softcap, both element types, d = 64 / 128 /
+ *             192, merge / direct 16-bit / direct f32 out, max_logits,
+ *             cu_margin). In merge mode a workgroup takes the locks of all G
+ *             heads, ordered so that packed and unpacked launches may
+ *             accumulate into one out. Results are within rounding of
+ *             magi_ffa_fwd's, not bit-equal: packing changes which rows share
+ *             a wave, and the deferred-max decision is per wave. With
+ *             hq == hk this is the pack_gqa = 0 launch. The launcher takes 4
+ *             waves when max_seqlen_q * G <= 128 and 8 otherwise (d = 192:
+ *             always 4); MAGI_FWD_WAVES overrides as for magi_ffa_fwd,
+ *             MAGI_FWD_NBUF is not read (each width runs its default ring).
+ *   reserved  must be 0.
+ * Validation with pack_gqa = 1, in this order, all before any HIP call: -1
+ * null pointer, -2 head dim, -3 hq % hk != 0, -9 elem_type, -14 reserved != 0;
+ * then n_ranges <= 0 returns 0 without a launch; -4 merge mode without locks,
+ * -5 more than 65535 ranges, -10 merge mode into a 16-bit out. There is no
+ * fp8 pack entry. magi_ffa_fwd_pack_args_size is sizeof of the struct as
+ * compiled (magi_ffa_args_size keeps its list). */
+typedef struct magi_ffa_fwd_pack_args {
+  magi_ffa_fwd_args args;
+  int32_t pack_gqa;
+  int32_t reserved;         /* must be 0 */
+} magi_ffa_fwd_pack_args;
+
+int magi_ffa_fwd_pack(const magi_ffa_fwd_pack_args* args);
+int magi_ffa_fwd_pack_args_size(void);
+
 typedef struct magi_ffa_bwd_args {
   const void* dout;         /* elem_type [total_q, hq, d] */
   const void* q;            /* elem_type [total_q, hq, d] */

@@ -57,6 +57,19 @@ class MagiFfaFwdArgs(ctypes.Structure):
     ]
 
 
+class MagiFfaFwdPackArgs(MagiFfaFwdArgs):
+    """mirrors magi_ffa_fwd_pack_args: magi_ffa_fwd_args embedded first (see
+    MagiFfaBwdDirectArgs), then the pack_gqa switch of magi_ffa_fwd_pack. An
+    instance also passes as the MagiFfaFwdArgs it starts with."""
+
+    _fields_ = [
+        # 1: a workgroup owns a KV head and packs the (token, q head) pairs of
+        # its GQA group into its q tiles; 0: magi_ffa_fwd's launch
+        ("pack_gqa", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),  # must be 0
+    ]
+
+
 class MagiFfaBwdArgs(ctypes.Structure):
     _fields_ = [
         ("dout", ctypes.c_void_p),
@@ -262,6 +275,8 @@ def _try_load() -> ctypes.CDLL | None:
         for name, argtypes in [
             ("magi_ffa_fwd", [ctypes.POINTER(MagiFfaFwdArgs)]),
             ("magi_ffa_fwd_fp8", [ctypes.POINTER(MagiFfaFwdArgs)]),
+            ("magi_ffa_fwd_pack", [ctypes.POINTER(MagiFfaFwdPackArgs)]),
+            ("magi_ffa_fwd_pack_args_size", []),
             ("magi_ffa_fwd_index", [ctypes.POINTER(MagiFfaIndexArgs)]),
             ("magi_ffa_fwd_index_fp8", [ctypes.POINTER(MagiFfaIndexArgs)]),
             ("magi_ffa_bwd_index", [ctypes.POINTER(MagiFfaIndexBwdArgs)]),
@@ -313,6 +328,7 @@ def _try_load() -> ctypes.CDLL | None:
         # a mirror of another size than the struct as compiled would make a
         # kernel read garbage pointers
         for cls, size in [
+            (MagiFfaFwdPackArgs, lib.magi_ffa_fwd_pack_args_size()),
             (MagiFfaBwdDirectArgs, lib.magi_ffa_bwd_direct_args_size()),
             (MagiFfaBwdCatArgs, lib.magi_ffa_bwd_cat_args_size()),
         ]:

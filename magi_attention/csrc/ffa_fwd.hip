@@ -69,8 +69,26 @@ struct FwdParams {
 // kernels): 8 waves (one 512-thread WG/CU = 2 waves/SIMD) halve the staging
 // and barrier cost per MFMA for long ranges; 4 for short ranges.
 // ET: bf16_t or f16_t (ElemTraits, ffa_device.h); P is rounded to ET before PV.
+//
+// PACK (pack_gqa): the work item's head is a KV head, and the q range's row
+// space is its (token, q head) pairs, G = hq / hk heads minor:
+//   row r of range [qs, qe)  ->  token qs + r / G, q head kh * G + r % G,
+//   R = (qe - qs) * G rows.
+// The G heads of a token are contiguous in q and all read the same K/V rows;
+// the swapped QK^T gives every lane one q column with a softmax state of its
+// own, and nothing in the k loop asks that the 32 columns of a wave be 32
+// tokens of one head. So a 16-token q block at G = 8 fills four 32-row MFMA
+// tiles in ONE workgroup that stages K/V once, where the unpacked launch
+// runs eight workgroups with half a live wave each. K/V staging, the ring,
+// the barrier accounting, defer-max, the P repack and the PV pipeline see
+// rows only. What knows about tokens: the Q load, the mask compares (the
+// lane's token), the k bounds (first and last token of a wave / block; with
+// G = 3 a token's heads straddle two waves) and the epilogue (per-row
+// token * hq + head). The divisions by the runtime G happen once per work
+// item, none inside the k loop. With PACK = false G is the constant 1 and
+// every expression below is the unpacked kernel's.
 template <class ET, int D, bool HAS_SOFTCAP, bool ATOMIC, bool OUT_16,
-          int WAVES, int NBUF = 2>
+          int WAVES, int NBUF = 2, bool PACK = false>
 __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
     FwdParams<ET> p) {
   using Tr = ElemTraits<ET>;
@@ -99,7 +117,9 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   const int h = p.head_major ? wx : wz;
   const int mb_lin = p.head_major ? wy : wx;
   const int qs = p.q_ranges[2 * ri], qe = p.q_ranges[2 * ri + 1];
-  const int nqb = (qe - qs + 32 * WAVES - 1) / (32 * WAVES);
+  const int G = PACK ? p.gqa : 1;
+  const int R = (qe - qs) * G;                // rows of the range
+  const int nqb = (R + 32 * WAVES - 1) / (32 * WAVES);
   if (mb_lin >= nqb) continue;                // uniform across block
   // auto_range_merge: iterate this unique q range's k segments in-kernel,
   // online softmax carried across them (reference merge_range.cu semantics)
@@ -113,7 +133,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   const int at0 =
       (p.attn_type_map && seg0 < seg1) ? p.attn_type_map[seg0] : 0;
   const int mb = (at0 == 1 || at0 == 3) ? nqb - 1 - mb_lin : mb_lin;
-  const int m0 = qs + mb * (32 * WAVES);
+  const int rb = mb * (32 * WAVES);           // block's first row
   int ks, ke, atype;
 
   const int lane = threadIdx.x & 63;
@@ -126,11 +146,24 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   const int lo32 = lane & 31;
   const int hi = lane >> 5;
 
-  const int q0 = m0 + wave * 32;
-  const int qrow = q0 + lo32;
-  const bool qvalid = (qrow < qe) && (q0 < qe);
-  const bool qvalid_any = q0 < qe;
-  const int qclamp = qvalid ? qrow : (qe - 1);
+  const int rw = rb + wave * 32;              // wave's first row
+  const bool qvalid = rw + lo32 < R;
+  const bool qvalid_any = rw < R;
+  const int rclamp = qvalid ? rw + lo32 : R - 1;
+  // the lane's token and q head. A dead lane loads the range's last row and
+  // stores nothing; every other use of qrow sits behind qvalid, so the
+  // unpacked kernel keeps the unclamped token, which costs no live register.
+  const int qrow = PACK ? qs + rclamp / G : qs + rw + lo32;
+  const int qload = PACK ? qrow : qs + rclamp;
+  // q head from the token, without a second division; the epilogue calls it
+  // again, so that only qrow stays live across the k loop
+  auto head_of = [&](int tok) {
+    return PACK ? h * G + (rclamp - (tok - qs) * G) : h;
+  };
+  // first and last token the wave (tw0, tw1) and the block (tb0, tb1) cover
+  const int tw0 = qs + rw / G, tw1 = qs + min(rw + 31, R - 1) / G;
+  const int tb0 = qs + rb / G;
+  const int tb1 = qs + min(rb + 32 * WAVES - 1, R - 1) / G;
 
   // softmax scales (reference mainloop_fwd...hpp:466-489)
   const float sl2 = HAS_SOFTCAP ? p.softcap * 1.4426950408889634f
@@ -141,18 +174,16 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   int n_lo = 0, n_hi = 0, b_lo = 0, b_hi = 0;
   auto seg_bounds = [&]() {
     n_lo = ks; n_hi = ke;
-    if (ke > ks && q0 < qe) {
-      const int qhiw = min(q0 + 31, qe - 1);
-      if (atype == 1 || atype == 3) n_hi = min(n_hi, qhiw + (ke - qe) + 1);
-      if (atype == 2 || atype == 3) n_lo = max(n_lo, q0 + (ks - qs));
+    if (ke > ks && qvalid_any) {
+      if (atype == 1 || atype == 3) n_hi = min(n_hi, tw1 + (ke - qe) + 1);
+      if (atype == 2 || atype == 3) n_lo = max(n_lo, tw0 + (ks - qs));
     } else {
       n_hi = n_lo;  // empty
     }
     b_lo = ks; b_hi = ke;
-    if (ke > ks && m0 < qe) {
-      const int qhib = min(m0 + 32 * WAVES - 1, qe - 1);
-      if (atype == 1 || atype == 3) b_hi = min(b_hi, qhib + (ke - qe) + 1);
-      if (atype == 2 || atype == 3) b_lo = max(b_lo, m0 + (ks - qs));
+    if (ke > ks) {  // rb < R: mb < nqb
+      if (atype == 1 || atype == 3) b_hi = min(b_hi, tb1 + (ke - qe) + 1);
+      if (atype == 2 || atype == 3) b_lo = max(b_lo, tb0 + (ks - qs));
     } else {
       b_hi = b_lo;
     }
@@ -191,13 +222,13 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   // Q fragments in registers (8 x vec8 for D=128)
   vec8 qf[DF];
   {
-    const ET* qp = p.q + (size_t)qclamp * p.hq * D + (size_t)h * D;
+    const ET* qp = p.q + (size_t)qload * p.hq * D + (size_t)head_of(qload) * D;
 #pragma unroll
     for (int dd = 0; dd < DF; ++dd)
       qf[dd] = *(const vec8*)(qp + dd * 16 + hi * 8);
   }
 
-  const int kh = h / p.gqa;
+  const int kh = PACK ? h : h / p.gqa;
   const size_t k_pitch = (size_t)p.hk * D;
   const ET* kbase = p.k + (size_t)kh * D;
   const ET* vbase = p.v + (size_t)kh * D;
@@ -253,10 +284,12 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
     // interior fast path: when the whole tile is provably unmasked for every
     // lane (wave-uniform), skip the per-element compare/select chain — the
     // kernels are instruction-issue-bound and masks only bind near edges.
+    // All 32 rows valid (then tw1 is the token of row rw + 31), and unmasked
+    // for the wave's lowest token (causal) and its highest (inv-causal).
     const bool interior =
-        (q0 + 31 < qe) && (ns >= n_lo) && (ns + FFA_BN <= n_hi) &&
-        !((atype == 1 || atype == 3) && (ns + FFA_BN - 1 > q0 + (ke - qe))) &&
-        !((atype == 2 || atype == 3) && (ns < q0 + 31 + (ks - qs)));
+        (rw + 31 < R) && (ns >= n_lo) && (ns + FFA_BN <= n_hi) &&
+        !((atype == 1 || atype == 3) && (ns + FFA_BN - 1 > tw0 + (ke - qe))) &&
+        !((atype == 2 || atype == 3) && (ns < tw1 + (ks - qs)));
     float t[16];
     float mx = -INFINITY;
     if (interior) {
@@ -427,35 +460,54 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   if (any_seg) {
 
   // ======================= epilogue =======================
+  const int hrow = head_of(qrow);
   if (p.max_logits) {
     // per-head max of the scaled (softcapped) logits; m_run is the row max
     // in the exp2 domain -> x ln2. Empty rows are -inf and drop out.
     float ml = m_run * 0.6931471805599453f;
+    if constexpr (PACK) {
+      // a wave's lanes belong to different heads: one atomic per live row
+      // (both halves of a column hold the same m_run)
+      if (qvalid && hi == 0 && ml != -INFINITY)
+        unsafeAtomicMax(p.max_logits + hrow, ml);
+    } else {
 #pragma unroll
-    for (int off = 32; off; off >>= 1)
-      ml = fmaxf(ml, __shfl_xor(ml, off, 64));
-    if (lane == 0 && ml != -INFINITY)
-      unsafeAtomicMax(p.max_logits + h, ml);
+      for (int off = 32; off; off >>= 1)
+        ml = fmaxf(ml, __shfl_xor(ml, off, 64));
+      if (lane == 0 && ml != -INFINITY)
+        unsafeAtomicMax(p.max_logits + h, ml);
+    }
   }
   const float lse_new =
       (l_run > 0.f) ? (m_run + __log2f(l_run)) * 0.6931471805599453f : -INFINITY;
   const float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
 
-  const size_t out_row_pitch = (size_t)p.hq * D;
+  // out / lse row of a lane: token * hq + head. PACK carries it per lane as
+  // 32 bits (total_q * hq rows; lse alone is 4 bytes a row) and moves it with
+  // the inv_l / w_prev / w_new bpermutes to the lanes that store the row.
+  const size_t orow = (size_t)qrow * p.hq + hrow;
+  // first out element of row `src` of the wave's tile
+  auto out_base = [&](int src) -> size_t {
+    if constexpr (PACK)
+      return (size_t)__builtin_amdgcn_ds_bpermute(src << 2, (unsigned)orow) * D;
+    else
+      return ((size_t)(qs + rw + src) * p.hq + h) * D;
+  };
 
   if (!ATOMIC) {
     // direct store: q_ranges guaranteed disjoint; rows with l==0 keep initial
+    // PACK: rows are distinct (token, head) pairs, so disjoint q ranges still
+    // mean one owner per element
     if (l_run > 0.f && qvalid && hi == 0)
-      p.lse[(size_t)qrow * p.hq + h] = lse_new;
+      p.lse[orow] = lse_new;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int src = crow(r, hi);
       const float ilq = __uint_as_float(
           __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(inv_l)));
-      const int qr = q0 + src;
-      const bool valid = (qr < qe) && ilq > 0.f;
+      const size_t base = out_base(src);  // every lane: bpermute
+      const bool valid = (rw + src < R) && ilq > 0.f;
       if (!valid) continue;
-      const size_t base = (size_t)qr * out_row_pitch + (size_t)h * D;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         const float val = acc_o[dt][r] * ilq;
@@ -470,23 +522,32 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   // ---- lock-guarded read-merge-write (range locks; a 32*WAVES-row block
   // spans up to 32*WAVES/LOCK_GRAN+1 slots, acquired in ascending order —
   // the global order prevents deadlock between overlapping blocks) ----
-  const int row_last = min(m0 + 32 * WAVES, qe) - 1;
-  const int s0 = m0 / LOCK_GRAN, s1 = row_last / LOCK_GRAN;
+  // PACK: the block covers tokens [tb0, tb1] for all G heads of its KV head
+  // and takes lock (slot, kh * G + j) for each, slots ascending and within a
+  // slot heads ascending: lexicographic in (slot, head). The unpacked kernel
+  // takes (slot ascending, one fixed head), a chain in that same total order.
+  // Every holder therefore acquires along one total order over all locks, no
+  // wait cycle can form, and packed and unpacked launches that accumulate
+  // into one out (the CP runtime's out_acc) cannot deadlock each other.
+  const int s0 = tb0 / LOCK_GRAN, s1 = tb1 / LOCK_GRAN;
+  const int hl0 = h * G;  // first q head locked; G of them
   if (threadIdx.x == 0) {
     for (int sl = s0; sl <= s1; ++sl) {
-      int* lk = p.locks + (size_t)sl * p.hq + h;
-      int expected = 0;
-      while (!__hip_atomic_compare_exchange_strong(
-          lk, &expected, 1, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED,
-          __HIP_MEMORY_SCOPE_AGENT))
-        expected = 0;
+      for (int j = 0; j < G; ++j) {
+        int* lk = p.locks + (size_t)sl * p.hq + hl0 + j;
+        int expected = 0;
+        while (!__hip_atomic_compare_exchange_strong(
+            lk, &expected, 1, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED,
+            __HIP_MEMORY_SCOPE_AGENT))
+          expected = 0;
+      }
     }
   }
   __syncthreads();
 
   // merged lse per lane (q = lo32 layout)
   float lse_prev = -INFINITY;
-  if (qvalid) lse_prev = p.lse[(size_t)qrow * p.hq + h];
+  if (qvalid) lse_prev = p.lse[orow];
   float lse_m;
   {
     const float a = fmaxf(lse_prev, lse_new);
@@ -498,7 +559,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   const float w_new = (lse_new == -INFINITY) ? 0.f : expf(lse_new - lse_m) * inv_l;
 
   if (qvalid && lse_m != -INFINITY && hi == 0)
-    p.lse[(size_t)qrow * p.hq + h] = lse_m;
+    p.lse[orow] = lse_m;
 
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -507,9 +568,8 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
         __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(w_prev)));
     const float wn = __uint_as_float(
         __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(w_new)));
-    const int qr = q0 + src;
-    if (qr >= qe || (wp == 0.f && wn == 0.f)) continue;
-    const size_t base = (size_t)qr * out_row_pitch + (size_t)h * D;
+    const size_t base = out_base(src);  // every lane: bpermute
+    if (rw + src >= R || (wp == 0.f && wn == 0.f)) continue;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       float* ptr = p.out_f32 + base + dt * 32 + lo32;
@@ -524,8 +584,9 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   if (threadIdx.x == 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     for (int sl = s1; sl >= s0; --sl)
-      __hip_atomic_store(p.locks + (size_t)sl * p.hq + h, 0, __ATOMIC_RELEASE,
-                         __HIP_MEMORY_SCOPE_AGENT);
+      for (int j = G - 1; j >= 0; --j)
+        __hip_atomic_store(p.locks + (size_t)sl * p.hq + hl0 + j, 0,
+                           __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
   }  // ATOMIC epilogue
   }  // any_seg
@@ -583,7 +644,7 @@ extern "C" int magi_probe_mfma(const void* a, const void* b, void* d,
 // ------------------------------------------------------------------
 // launcher
 // ------------------------------------------------------------------
-template <class ET, int D, int W, int NB>
+template <class ET, int D, int W, int NB, bool PACK = false>
 static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams<ET>& p,
                         dim3 grid, dim3 block, hipStream_t stream) {
   const bool sc = a->softcap > 0.f;
@@ -591,8 +652,8 @@ static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams<ET>& p,
   const bool o16 = !a->out_is_fp32;
   if (atomic && o16) return -10;  // atomic merge requires fp32 out
 #define LAUNCH(SC, AT, OB)                                                 \
-  hipLaunchKernelGGL((ffa_fwd_kernel<ET, D, SC, AT, OB, W, NB>), grid,     \
-                     block, 0, stream, p)
+  hipLaunchKernelGGL((ffa_fwd_kernel<ET, D, SC, AT, OB, W, NB, PACK>),     \
+                     grid, block, 0, stream, p)
   if (atomic) {
     if (sc) LAUNCH(true, true, false);
     else LAUNCH(false, true, false);
@@ -607,9 +668,10 @@ static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams<ET>& p,
   return (int)hipGetLastError();
 }
 
-// magi_ffa_fwd past its validation, for one element type
+// magi_ffa_fwd past its validation, for one element type. pack: the PACK
+// kernel (magi_ffa_fwd_pack with pack_gqa set and hq != hk).
 template <class ET>
-static int fwd_entry(const magi_ffa_fwd_args* a) {
+static int fwd_entry(const magi_ffa_fwd_args* a, bool pack = false) {
   FwdParams<ET> p;
   p.q = (const ET*)a->q;
   p.k = (const ET*)a->k;
@@ -636,10 +698,18 @@ static int fwd_entry(const magi_ffa_fwd_args* a) {
   // TF) and 64k (742 vs 716) — the r1 preference for 4 predated the
   // scheduler-visible tr16 reads, packed converts and raw-exp2 softmax.
   int fw = 8;
+  // rows of the longest q range: tokens, under pack (token, head) pairs
+  const long long max_rows =
+      (long long)a->max_seqlen_q * (pack ? p.gqa : 1);
+  // pack: when the longest range fits one 4-wave block, 8 waves would leave
+  // half the workgroup without a row. The threshold is tile fill alone; what
+  // was measured is in profiles/fwd_pack_gqa.md.
+  if (pack && max_rows <= 128) fw = 4;
   { const char* e = getenv("MAGI_FWD_WAVES"); if (e && atoi(e)) fw = atoi(e); }
   if (a->d == 192) fw = 4;  // the W8 D=192 build spills (256-reg cap)
   const int span = 32 * fw;
-  const int mblocks = (a->max_seqlen_q + span - 1) / span;
+  const int mblocks = (int)((max_rows + span - 1) / span);
+  const int heads = pack ? a->hk : a->hq;  // head dimension of the work space
   if (a->n_ranges > 65535) return -5;
   // head-major XCD affinity (grid.x = head): late-r2 A/B moved the
   // threshold from 4 MB to 16 MB of per-head K+V — head-major wins 1.26x
@@ -650,8 +720,8 @@ static int fwd_entry(const magi_ffa_fwd_args* a) {
   { const char* e = getenv("MAGI_FWD_HEADMAJOR");  // A/B override
     if (e) p.head_major = atoi(e) ? 1 : 0; }
   dim3 grid = p.head_major
-                  ? dim3(a->hq, mblocks, (unsigned)a->n_ranges)
-                  : dim3(mblocks, (unsigned)a->n_ranges, a->hq);
+                  ? dim3(heads, mblocks, (unsigned)a->n_ranges)
+                  : dim3(mblocks, (unsigned)a->n_ranges, heads);
   p.work_nx = grid.x;
   p.work_ny = grid.y;
   p.work_nz = grid.z;
@@ -672,6 +742,19 @@ static int fwd_entry(const magi_ffa_fwd_args* a) {
   // and W4 runs 2 WGs/CU which the 96 KB ring would halve)
   int nbuf = 3;
   { const char* e = getenv("MAGI_FWD_NBUF"); if (e) nbuf = atoi(e); }
+  // pack is built for each (D, WAVES) pair's default ring depth only, to keep
+  // the instantiation count in hand: MAGI_FWD_NBUF is not read under pack
+  if (pack) {
+    if (a->d == 192)
+      return launch_fwd_d<ET, 192, 4, 2, true>(a, p, grid, block, stream);
+    if (a->d == 64)
+      return fw == 8
+                 ? launch_fwd_d<ET, 64, 8, 3, true>(a, p, grid, block, stream)
+                 : launch_fwd_d<ET, 64, 4, 2, true>(a, p, grid, block, stream);
+    return fw == 8
+               ? launch_fwd_d<ET, 128, 8, 3, true>(a, p, grid, block, stream)
+               : launch_fwd_d<ET, 128, 4, 2, true>(a, p, grid, block, stream);
+  }
   if (a->d == 64)
     return fw == 8
                ? (nbuf == 3
@@ -697,6 +780,26 @@ extern "C" int magi_ffa_fwd(const magi_ffa_fwd_args* a) {
   if (!a->disable_atomic_reduction && !a->locks) return -4;
   return a->elem_type == MAGI_FFA_ELEM_FP16 ? fwd_entry<f16_t>(a)
                                             : fwd_entry<bf16_t>(a);
+}
+
+extern "C" int magi_ffa_fwd_pack(const magi_ffa_fwd_pack_args* pa) {
+  if (!pa) return -1;
+  const magi_ffa_fwd_args* a = &pa->args;
+  if (!pa->pack_gqa) return magi_ffa_fwd(a);
+  if (!a->q || !a->k || !a->v || !a->out || !a->lse) return -1;
+  if (a->d != 64 && a->d != 128 && a->d != 192) return -2;
+  if (a->hq % a->hk != 0) return -3;
+  if (!elem_type_known(a->elem_type)) return -9;
+  if (pa->reserved != 0) return -14;
+  if (a->n_ranges <= 0) return 0;
+  if (!a->disable_atomic_reduction && !a->locks) return -4;
+  const bool pack = a->hq != a->hk;  // a group of one head: the plain launch
+  return a->elem_type == MAGI_FFA_ELEM_FP16 ? fwd_entry<f16_t>(a, pack)
+                                            : fwd_entry<bf16_t>(a, pack);
+}
+
+extern "C" int magi_ffa_fwd_pack_args_size(void) {
+  return (int)sizeof(magi_ffa_fwd_pack_args);
 }
 
 extern "C" int magi_ffa_args_size(int which) {

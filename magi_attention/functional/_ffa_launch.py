@@ -138,15 +138,26 @@ def bwd_dsink(sink_f, s_sink, ssh, lse, dpsum, dsink=None) -> torch.Tensor:
 
 
 # ---------------- dense forward ----------------
+def pack_gqa_active(pack_gqa, dtype: torch.dtype, hq: int, hk: int) -> bool:
+    """Whether a forward with this flag runs the packed kernel: there is a GQA
+    group to pack and a 16-bit kernel to pack it in (no fp8 pack entry).
+    Otherwise the flag is accepted and the unpacked launch runs."""
+    return bool(pack_gqa) and hq != hk and dtype != _FP8
+
+
 def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
         max_logits, qk_starts, max_seqlen_q, softmax_scale, softcap,
-        disable_fwd_atomic_reduction, sm_margin, deterministic) -> None:
+        disable_fwd_atomic_reduction, sm_margin, deterministic,
+        pack_gqa=False) -> None:
     """Dense forward into (out, lse): the fp8 entry or the 16-bit one (bf16 or
     fp16 by elem_type) by q.dtype;
-    deterministic = fixed merge order, one launch per q-disjoint range group."""
+    deterministic = fixed merge order, one launch per q-disjoint range group;
+    pack_gqa = a workgroup owns a KV head and packs the (token, q head) pairs
+    of its group into its q tiles (where pack_gqa_active)."""
     tq, hq, d = q.shape
     tk, hk, _ = k.shape
-    args = _ffa_lib.MagiFfaFwdArgs(
+    pack = pack_gqa_active(pack_gqa, q.dtype, hq, hk)
+    args = (_ffa_lib.MagiFfaFwdPackArgs if pack else _ffa_lib.MagiFfaFwdArgs)(
         q=ptr(q), k=ptr(k), v=ptr(v), out=ptr(out), lse=ptr(lse),
         q_ranges=ptr(q_ranges), k_ranges=ptr(k_ranges),
         attn_type_map=ptr(attn_type_map), locks=ptr(locks),
@@ -161,6 +172,9 @@ def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
     )
     lib = _ffa_lib.lib()
     fn = lib.magi_ffa_fwd_fp8 if q.dtype == _FP8 else lib.magi_ffa_fwd
+    if pack:
+        args.pack_gqa = 1
+        fn = lib.magi_ffa_fwd_pack
     if deterministic and q_ranges.shape[0] > 1:
         groups = _color_ranges(q_ranges.cpu().tolist())
         launch_per_group(args, q_ranges, k_ranges, attn_type_map,

@@ -119,12 +119,15 @@ def _flex_flash_attn_forward(
     max_seqlen_q: Optional[int] = None,
     max_logits: Optional[torch.Tensor] = None,
     qk_starts: Optional[torch.Tensor] = None,
+    pack_gqa: bool = False,
     **_unused,
 ) -> tuple[torch.Tensor, AttnForwardMeta]:
     """Dense (range-table) forward into (out, lse). q/k/v are all bf16, all
     fp16 or all fp8-e4m3. In merge mode out is an f32 accumulator; with
     disable_fwd_atomic_reduction it defaults to q's dtype, stored directly by
     the kernel, and a 16-bit out or out_type must be q's own 16-bit type.
+    pack_gqa runs the packed kernel where _ffa_launch.pack_gqa_active says so
+    (bf16 / fp16 and hq != hk) and today's launch otherwise.
 
     fp16 direct store with a sink: the sink postprocess kernel reads a 16-bit
     out as bf16, so it must never see fp16. That combination therefore runs
@@ -191,7 +194,7 @@ def _flex_flash_attn_forward(
         max_seqlen_q=max_seqlen_q, softmax_scale=softmax_scale,
         softcap=softcap,
         disable_fwd_atomic_reduction=disable_fwd_atomic_reduction,
-        sm_margin=sm_margin, deterministic=deterministic,
+        sm_margin=sm_margin, deterministic=deterministic, pack_gqa=pack_gqa,
     )
     if sink is not None:
         assert out.dtype != torch.float16  # the postprocess reads 16 bits as bf16
@@ -631,7 +634,7 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             disable_fwd_atomic_reduction=disable_fwd_atomic_reduction,
             deterministic=deterministic, sm_margin=sm_margin,
             max_seqlen_q=max_seqlen_q, max_logits=max_logits,
-            qk_starts=fwd_qk_starts,
+            qk_starts=fwd_qk_starts, pack_gqa=pack_gqa,
         )
         lse = meta.lse
         # fp8 extension returns bf16 out
@@ -746,6 +749,20 @@ def flex_flash_attn_func(
     deterministic, auto_range_merge, direct store). P and dS are rounded to
     fp16 before their MFMAs and accumulate in fp32. Mixed 16-bit dtypes are
     rejected; index_attn_indices stays bf16 / fp8 only.
+
+    pack_gqa=True (range path, bf16 / fp16, it acts when hq != hk): a forward
+    workgroup owns a KV head and fills its 32-row q tiles with the (token,
+    q head) pairs of the GQA group, heads minor, staging K/V once for the
+    whole group, where the default launch gives every q head workgroups of
+    its own with 32 consecutive tokens per wave. It is meant for short q
+    ranges (block-sparse tables, short documents; most useful together with
+    auto_range_merge), where the default leaves most of each wave empty; on
+    long ranges nothing is gained. From which q-range length it stops paying
+    is measured in profiles/fwd_pack_gqa.md. out, lse and max_logits keep
+    their layout and agree with the default launch within rounding (not bit
+    for bit); every other option composes with it, and the backward is the
+    usual one. fp8 inputs, index_attn_indices and hq == hk accept the flag
+    and run the default launch.
 
     Backward stores (range path, bf16 / fp16). By default dq, dk and dv are
     accumulated with atomics in f32 buffers and cast once at the end.
