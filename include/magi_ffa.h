@@ -117,6 +117,60 @@ typedef struct magi_ffa_fwd_pack_args {
 int magi_ffa_fwd_pack(const magi_ffa_fwd_pack_args* args);
 int magi_ffa_fwd_pack_args_size(void);
 
+/* sparse_load (reference flex_flash_attn_func sparse_load: "k_range size is
+ * small (< 64)", to be used with auto_range_merge). Under qk_starts the
+ * forward serves a unique q range's k segments one after another, each with
+ * whole 64-row K/V stages of its own, a ring restart, a drain and a barrier:
+ * with k blocks of 16 or 32 rows most of every stage and MFMA tile is
+ * padding. The switch rides behind an embedded copy of the pack struct, as
+ * pack_gqa rides behind magi_ffa_fwd_args:
+ *   sparse_load 0: exactly magi_ffa_fwd_pack(&pack), bit for bit; k_cum and
+ *             reserved are not read.
+ *             1: the k rows of unique q range ri are one virtual axis, the
+ *             segments k_ranges[qk_starts[ri] .. qk_starts[ri + 1]) laid end
+ *             to end in table order: L = sum of (ke - ks) rows. Empty
+ *             segments add nothing, segments may come in any k order and
+ *             length (1 included), and a segment listed twice counts twice,
+ *             as it does with sparse_load = 0. The k loop stages 64 virtual
+ *             rows at a time through a row map the workgroup keeps in LDS
+ *             (2048 rows; longer axes are walked in chunks), so every K/V
+ *             stage and every MFMA tile but a chunk's last is full.
+ *             Every segment is a full block (type 0): attn_type_map is NOT
+ *             read, and the caller vouches for it as it does for disjoint
+ *             ranges. qk_starts is required. A range with L = 0 leaves out
+ *             and lse untouched. out, lse and max_logits have the usual
+ *             layout and meaning and are within rounding of the
+ *             sparse_load = 0 result, not bit-equal (the tile composition
+ *             changes). pack.pack_gqa, softcap, both element types, merge /
+ *             direct 16-bit / direct f32 out, max_logits and cu_margin
+ *             compose with it. Built for d = 64 and 128; d = 192 runs the
+ *             sparse_load = 0 launch (k_cum unread) and is not an error. The
+ *             launcher takes 4 waves when the longest q range has at most
+ *             128 (packed) rows and 8 otherwise; MAGI_FWD_WAVES overrides,
+ *             MAGI_FWD_NBUF is not read.
+ *   k_cum     int32 [n_segments + 1], n_segments = qk_starts[n_ranges]:
+ *             k_cum[0] = 0, k_cum[s + 1] = k_cum[s] + max(ke_s - ks_s, 0)
+ *             over k_ranges (a device cumsum; no host sync). A k_cum that
+ *             disagrees with k_ranges gives wrong results; mapped rows are
+ *             clamped to [0, total_k).
+ *   reserved  must be 0, like pack.reserved.
+ * Validation with sparse_load = 1, in this order, all before any HIP call:
+ * -1 null pointer, -2 head dim, -3 hq % hk != 0, -9 elem_type, -14 reserved
+ * or pack.reserved != 0, -15 qk_starts == NULL, -1 k_cum == NULL; then
+ * n_ranges <= 0 returns 0 without a launch; -4 merge mode without locks, -5
+ * more than 65535 ranges, -10 merge mode into a 16-bit out. There is no fp8
+ * sparse entry. magi_ffa_fwd_sparse_args_size is sizeof of the struct as
+ * compiled. */
+typedef struct magi_ffa_fwd_sparse_args {
+  magi_ffa_fwd_pack_args pack;
+  const int32_t* k_cum;
+  int32_t sparse_load;
+  int32_t reserved;         /* must be 0 */
+} magi_ffa_fwd_sparse_args;
+
+int magi_ffa_fwd_sparse(const magi_ffa_fwd_sparse_args* args);
+int magi_ffa_fwd_sparse_args_size(void);
+
 typedef struct magi_ffa_bwd_args {
   const void* dout;         /* elem_type [total_q, hq, d] */
   const void* q;            /* elem_type [total_q, hq, d] */

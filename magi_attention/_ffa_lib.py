@@ -70,6 +70,21 @@ class MagiFfaFwdPackArgs(MagiFfaFwdArgs):
     ]
 
 
+class MagiFfaFwdSparseArgs(MagiFfaFwdPackArgs):
+    """mirrors magi_ffa_fwd_sparse_args: magi_ffa_fwd_pack_args embedded first,
+    then the sparse_load switch of magi_ffa_fwd_sparse and its table. An
+    instance also passes as the two structs it starts with."""
+
+    _fields_ = [
+        # int32 [n_segments + 1]: running sum of the k segment lengths
+        ("k_cum", ctypes.c_void_p),
+        # 1: a unique q range's k segments are packed into full K/V tiles
+        # (needs qk_starts, all segments full); 0: magi_ffa_fwd_pack's launch
+        ("sparse_load", ctypes.c_int32),
+        ("sparse_reserved", ctypes.c_int32),  # `reserved` in C; must be 0
+    ]
+
+
 class MagiFfaBwdArgs(ctypes.Structure):
     _fields_ = [
         ("dout", ctypes.c_void_p),
@@ -277,6 +292,8 @@ def _try_load() -> ctypes.CDLL | None:
             ("magi_ffa_fwd_fp8", [ctypes.POINTER(MagiFfaFwdArgs)]),
             ("magi_ffa_fwd_pack", [ctypes.POINTER(MagiFfaFwdPackArgs)]),
             ("magi_ffa_fwd_pack_args_size", []),
+            ("magi_ffa_fwd_sparse", [ctypes.POINTER(MagiFfaFwdSparseArgs)]),
+            ("magi_ffa_fwd_sparse_args_size", []),
             ("magi_ffa_fwd_index", [ctypes.POINTER(MagiFfaIndexArgs)]),
             ("magi_ffa_fwd_index_fp8", [ctypes.POINTER(MagiFfaIndexArgs)]),
             ("magi_ffa_bwd_index", [ctypes.POINTER(MagiFfaIndexBwdArgs)]),
@@ -329,6 +346,7 @@ def _try_load() -> ctypes.CDLL | None:
         # kernel read garbage pointers
         for cls, size in [
             (MagiFfaFwdPackArgs, lib.magi_ffa_fwd_pack_args_size()),
+            (MagiFfaFwdSparseArgs, lib.magi_ffa_fwd_sparse_args_size()),
             (MagiFfaBwdDirectArgs, lib.magi_ffa_bwd_direct_args_size()),
             (MagiFfaBwdCatArgs, lib.magi_ffa_bwd_cat_args_size()),
         ]:

@@ -38,6 +38,11 @@
 #define FFA_BM 128   // q rows per workgroup (4 waves x 32)
 #define FFA_BN 32    // k rows per inner tile
 #define LOCK_GRAN 128
+// SPARSE (sparse_load): rows of the virtual-k-row -> global-K-row map a
+// workgroup keeps in LDS behind the staging ring (8 KB). Longer virtual axes
+// are walked in chunks of this many rows. Sized so that the 4-wave D=128
+// kernel (64 KB ring) still fits two workgroups in a CU's 160 KB.
+#define SPARSE_MAP_ROWS 2048
 
 // ET: element type of q/k/v and of a 16-bit out, bf16_t or f16_t
 template <class ET>
@@ -63,6 +68,8 @@ struct FwdParams {
   float scale;        // softmax_scale
   float softcap;
   long long total_q, total_k;
+  const int* k_cum;   // SPARSE only: [n segments + 1] running sum of the k
+                      // segment lengths of k_ranges (see magi_ffa_fwd_sparse)
 };
 
 // WAVES: q-tiles per workgroup sharing ONE staged K/V image (see the bwd
@@ -87,10 +94,37 @@ struct FwdParams {
 // token * hq + head). The divisions by the runtime G happen once per work
 // item, none inside the k loop. With PACK = false G is the constant 1 and
 // every expression below is the unpacked kernel's.
+//
+// SPARSE (sparse_load, with qk_starts): the k side of the tile is packed the
+// way PACK packs the q side. The default kernel serves a unique q range's k
+// segments one by one: per segment it restarts the ring, stages whole 64-row
+// images whose rows clamp to the segment's last one, and ends in a drain and
+// a barrier, so a 16-row k block costs a full K and V stage, two more
+// nobody reads, and feeds one half-masked MFMA sub-tile. Here the range's k
+// rows are ONE virtual axis, its segments concatenated in table order
+// (L = sum of ke - ks; empty segments vanish, a repeated one counts twice),
+// and the k loop runs over that axis: 64 virtual rows per stage, whatever
+// segments they come from. All it takes is the row number each lane of the
+// LDS-DMA hands to stage_glds, which already gives every lane a source
+// address of its own:
+//   - the workgroup builds map[j] = global K row of virtual row j in LDS,
+//     behind the ring: thread t takes rows t, t + 64 * WAVES, ... and finds
+//     each row's segment by binary search in k_cum (tracked loads, retired
+//     by the barrier that publishes the map, before the k loop starts);
+//   - stage_glds reads kr = map[min(j, Lc - 1)], an LDS read: the k loop
+//     still holds no vector-memory op but the untracked stage loads, and
+//     pipe_barrier's vmcnt(GOPS) accounting is untouched;
+//   - a range longer than SPARSE_MAP_ROWS is walked in chunks; a chunk ends
+//     in the drain and barrier that end a segment in the default kernel, and
+//     the next chunk rebuilds the map behind them.
+// Every segment is full (type 0; the caller's promise, attn_type_map is not
+// read), so in virtual rows the bounds are [0, Lc): every tile but a chunk's
+// last takes the interior fast path, the tail tile the `kk < Lc` compare.
+// Softmax, defer-max, P repack, PV, max_logits and the epilogues see none of
+// this. With SPARSE = false no expression below changes.
 template <class ET, int D, bool HAS_SOFTCAP, bool ATOMIC, bool OUT_16,
-          int WAVES, int NBUF = 2, bool PACK = false>
-__global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
-    FwdParams<ET> p) {
+          int WAVES, int NBUF, bool PACK, bool SPARSE>
+DEV_INLINE void ffa_fwd_body(FwdParams<ET> p) {  // by value, as a kernel's
   using Tr = ElemTraits<ET>;
   using vec8 = typename Tr::x8;
   constexpr int DF = D / 16;    // # of 16-wide d fragments
@@ -131,7 +165,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   // of the flattened work index alone, so the exact grid and the cu_margin
   // strided walk agree on it.
   const int at0 =
-      (p.attn_type_map && seg0 < seg1) ? p.attn_type_map[seg0] : 0;
+      (!SPARSE && p.attn_type_map && seg0 < seg1) ? p.attn_type_map[seg0] : 0;
   const int mb = (at0 == 1 || at0 == 3) ? nqb - 1 - mb_lin : mb_lin;
   const int rb = mb * (32 * WAVES);           // block's first row
   int ks, ke, atype;
@@ -211,7 +245,10 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   // of the first tr16 V read of every subtile, one phase deep in effect.
   // The barrier's counted wait is the only vector-memory wait in the k loop.
   constexpr int KITER = 2 * FFA_BN;
-  __shared__ __attribute__((aligned(16))) char fsmem[NBUF * 2 * KITER * ROWB];
+  constexpr int RING_BYTES = NBUF * 2 * KITER * ROWB;
+  __shared__ __attribute__((aligned(16))) char
+      fsmem[RING_BYTES + (SPARSE ? SPARSE_MAP_ROWS * 4 : 0)];
+  int* const smap = (int*)(fsmem + RING_BYTES);  // SPARSE: the row map
   auto lds_k = [&](int buf) -> ET* {
     return (ET*)(fsmem + (2 * buf) * KITER * ROWB);
   };
@@ -254,7 +291,9 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
       const int r0 = (KITER / WAVES) * wave + ROWS_PER_GLDS * gi;
       const int r = r0 + lane / (ROWB / 16);
       const int c = lane % (ROWB / 16);
-      const int kr = min(n0x + r, ke - 1);
+      // SPARSE: n0x, r and ke count virtual rows of the chunk (ke = Lc)
+      const int kr = SPARSE ? smap[min(n0x + r, ke - 1)]
+                            : min(n0x + r, ke - 1);
       int cs = c ^ ((r & SW32M) << 1);
       if (cs >= VSLOTS) cs = 0;  // padding slot: any in-bounds source
       const int csw = cs * 8;
@@ -407,11 +446,42 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   };
 
   bool any_seg = false;
-  for (int seg = seg0; seg < seg1; ++seg) {
+  // SPARSE: `seg` counts chunks of the virtual k axis, not segments
+  const int cum0 = SPARSE ? p.k_cum[seg0] : 0;
+  const int vlen = SPARSE ? p.k_cum[seg1] - cum0 : 0;  // L, block-uniform
+  const int loop0 = SPARSE ? 0 : seg0;
+  const int loop1 =
+      SPARSE ? (vlen + SPARSE_MAP_ROWS - 1) / SPARSE_MAP_ROWS : seg1;
+  for (int seg = loop0; seg < loop1; ++seg) {
+    if constexpr (SPARSE) {
+      const int c0 = seg * SPARSE_MAP_ROWS;  // chunk's first virtual row
+      ks = 0;
+      ke = min(vlen - c0, SPARSE_MAP_ROWS);  // Lc >= 1
+      atype = 0;
+      // The ring is drained and every wave is past the barrier that ended
+      // the previous chunk or work item: nobody reads the map any more.
+      for (int j = threadIdx.x; j < ke; j += 64 * WAVES) {
+        const int x = cum0 + c0 + j;
+        // first segment boundary above x: k_cum[s] <= x < k_cum[s + 1] names
+        // a non-empty segment, and k_cum[seg1] = cum0 + L > x ends the search
+        int blo = seg0 + 1, bhi = seg1;
+        while (blo < bhi) {
+          const int mid = (blo + bhi) >> 1;
+          if (p.k_cum[mid] > x) bhi = mid;
+          else blo = mid + 1;
+        }
+        const int s = blo - 1;
+        const int row = p.k_ranges[2 * s] + (x - p.k_cum[s]);
+        // a k_cum that disagrees with k_ranges must not leave K and V
+        smap[j] = min(max(row, 0), (int)p.total_k - 1);
+      }
+      __syncthreads();
+    } else {
     ks = p.k_ranges[2 * seg];
     ke = p.k_ranges[2 * seg + 1];
     atype = p.attn_type_map ? p.attn_type_map[seg] : 0;
     if (ke <= ks) continue;  // uniform across block
+    }
     seg_bounds();
     if (b_lo >= b_hi) continue;
     any_seg = true;
@@ -593,6 +663,26 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
   }  // strided work loop
 }
 
+// The default kernels: names, template parameters and code as before SPARSE.
+template <class ET, int D, bool HAS_SOFTCAP, bool ATOMIC, bool OUT_16,
+          int WAVES, int NBUF = 2, bool PACK = false>
+__global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_fwd_kernel(
+    FwdParams<ET> p) {
+  ffa_fwd_body<ET, D, HAS_SOFTCAP, ATOMIC, OUT_16, WAVES, NBUF, PACK, false>(p);
+}
+
+// The SPARSE kernels have an entry of their own because they are built
+// without the packed-f32 VALU ops (v_pk_fma_f32 and kin), as every kernel
+// added from here on is, and that switch is per function. The body is
+// force-inlined into both entries and takes the caller's setting.
+template <class ET, int D, bool HAS_SOFTCAP, bool ATOMIC, bool OUT_16,
+          int WAVES, int NBUF, bool PACK>
+__global__ __launch_bounds__(64 * WAVES, 8 / WAVES)
+__attribute__((target("no-packed-fp32-ops"))) void ffa_fwd_sparse_kernel(
+    FwdParams<ET> p) {
+  ffa_fwd_body<ET, D, HAS_SOFTCAP, ATOMIC, OUT_16, WAVES, NBUF, PACK, true>(p);
+}
+
 // ------------------------------------------------------------------
 // MFMA layout probe (GPU self-test; see tests/test_ffa_gpu.py)
 // ------------------------------------------------------------------
@@ -644,7 +734,8 @@ extern "C" int magi_probe_mfma(const void* a, const void* b, void* d,
 // ------------------------------------------------------------------
 // launcher
 // ------------------------------------------------------------------
-template <class ET, int D, int W, int NB, bool PACK = false>
+template <class ET, int D, int W, int NB, bool PACK = false,
+          bool SPARSE = false>
 static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams<ET>& p,
                         dim3 grid, dim3 block, hipStream_t stream) {
   const bool sc = a->softcap > 0.f;
@@ -652,8 +743,15 @@ static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams<ET>& p,
   const bool o16 = !a->out_is_fp32;
   if (atomic && o16) return -10;  // atomic merge requires fp32 out
 #define LAUNCH(SC, AT, OB)                                                 \
-  hipLaunchKernelGGL((ffa_fwd_kernel<ET, D, SC, AT, OB, W, NB, PACK>),     \
-                     grid, block, 0, stream, p)
+  do {                                                                     \
+    if constexpr (SPARSE)                                                  \
+      hipLaunchKernelGGL(                                                  \
+          (ffa_fwd_sparse_kernel<ET, D, SC, AT, OB, W, NB, PACK>), grid,   \
+          block, 0, stream, p);                                            \
+    else                                                                   \
+      hipLaunchKernelGGL((ffa_fwd_kernel<ET, D, SC, AT, OB, W, NB, PACK>), \
+                         grid, block, 0, stream, p);                       \
+  } while (0)
   if (atomic) {
     if (sc) LAUNCH(true, true, false);
     else LAUNCH(false, true, false);
@@ -669,9 +767,12 @@ static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams<ET>& p,
 }
 
 // magi_ffa_fwd past its validation, for one element type. pack: the PACK
-// kernel (magi_ffa_fwd_pack with pack_gqa set and hq != hk).
+// kernel (magi_ffa_fwd_pack with pack_gqa set and hq != hk). k_cum: non-null
+// picks the SPARSE kernel (magi_ffa_fwd_sparse with sparse_load set, d != 192).
 template <class ET>
-static int fwd_entry(const magi_ffa_fwd_args* a, bool pack = false) {
+static int fwd_entry(const magi_ffa_fwd_args* a, bool pack = false,
+                     const int32_t* k_cum = nullptr) {
+  const bool sparse = k_cum != nullptr;
   FwdParams<ET> p;
   p.q = (const ET*)a->q;
   p.k = (const ET*)a->k;
@@ -693,6 +794,7 @@ static int fwd_entry(const magi_ffa_fwd_args* a, bool pack = false) {
   p.softcap = a->softcap;
   p.total_q = a->total_q;
   p.total_k = a->total_k;
+  p.k_cum = k_cum;
 
   // r2: 8 waves (one 512-thread WG/CU) now beat 4 on both 8k (505 vs 471
   // TF) and 64k (742 vs 716) — the r1 preference for 4 predated the
@@ -704,7 +806,9 @@ static int fwd_entry(const magi_ffa_fwd_args* a, bool pack = false) {
   // pack: when the longest range fits one 4-wave block, 8 waves would leave
   // half the workgroup without a row. The threshold is tile fill alone; what
   // was measured is in profiles/fwd_pack_gqa.md.
-  if (pack && max_rows <= 128) fw = 4;
+  // sparse: the same rule. Its tables are block-sparse ones with short q
+  // ranges, and two 4-wave workgroups per CU hide each other's map build.
+  if ((pack || sparse) && max_rows <= 128) fw = 4;
   { const char* e = getenv("MAGI_FWD_WAVES"); if (e && atoi(e)) fw = atoi(e); }
   if (a->d == 192) fw = 4;  // the W8 D=192 build spills (256-reg cap)
   const int span = 32 * fw;
@@ -744,6 +848,16 @@ static int fwd_entry(const magi_ffa_fwd_args* a, bool pack = false) {
   { const char* e = getenv("MAGI_FWD_NBUF"); if (e) nbuf = atoi(e); }
   // pack is built for each (D, WAVES) pair's default ring depth only, to keep
   // the instantiation count in hand: MAGI_FWD_NBUF is not read under pack
+  // sparse likewise, for d = 64 and 128, with pack off and on
+  if (sparse) {
+#define SPARSE_LAUNCH(DD, PK)                                                \
+  (fw == 8 ? launch_fwd_d<ET, DD, 8, 3, PK, true>(a, p, grid, block, stream) \
+           : launch_fwd_d<ET, DD, 4, 2, PK, true>(a, p, grid, block, stream))
+    if (a->d == 64)
+      return pack ? SPARSE_LAUNCH(64, true) : SPARSE_LAUNCH(64, false);
+    return pack ? SPARSE_LAUNCH(128, true) : SPARSE_LAUNCH(128, false);
+#undef SPARSE_LAUNCH
+  }
   if (pack) {
     if (a->d == 192)
       return launch_fwd_d<ET, 192, 4, 2, true>(a, p, grid, block, stream);
@@ -800,6 +914,30 @@ extern "C" int magi_ffa_fwd_pack(const magi_ffa_fwd_pack_args* pa) {
 
 extern "C" int magi_ffa_fwd_pack_args_size(void) {
   return (int)sizeof(magi_ffa_fwd_pack_args);
+}
+
+extern "C" int magi_ffa_fwd_sparse(const magi_ffa_fwd_sparse_args* sa) {
+  if (!sa) return -1;
+  const magi_ffa_fwd_args* a = &sa->pack.args;
+  if (!sa->sparse_load) return magi_ffa_fwd_pack(&sa->pack);
+  if (!a->q || !a->k || !a->v || !a->out || !a->lse) return -1;
+  if (a->d != 64 && a->d != 128 && a->d != 192) return -2;
+  if (a->hq % a->hk != 0) return -3;
+  if (!elem_type_known(a->elem_type)) return -9;
+  if (sa->reserved != 0 || sa->pack.reserved != 0) return -14;
+  if (!a->qk_starts) return -15;  // the virtual k axis is a merged table's
+  if (!sa->k_cum) return -1;
+  if (a->n_ranges <= 0) return 0;
+  if (!a->disable_atomic_reduction && !a->locks) return -4;
+  const bool pack = sa->pack.pack_gqa && a->hq != a->hk;
+  // no SPARSE build at d = 192: the segment loop, k_cum unread
+  const int32_t* k_cum = a->d == 192 ? nullptr : sa->k_cum;
+  return a->elem_type == MAGI_FFA_ELEM_FP16 ? fwd_entry<f16_t>(a, pack, k_cum)
+                                            : fwd_entry<bf16_t>(a, pack, k_cum);
+}
+
+extern "C" int magi_ffa_fwd_sparse_args_size(void) {
+  return (int)sizeof(magi_ffa_fwd_sparse_args);
 }
 
 extern "C" int magi_ffa_args_size(int which) {

@@ -145,19 +145,33 @@ def pack_gqa_active(pack_gqa, dtype: torch.dtype, hq: int, hk: int) -> bool:
     return bool(pack_gqa) and hq != hk and dtype != _FP8
 
 
+def sparse_load_active(sparse_load, dtype: torch.dtype, d: int,
+                       qk_starts) -> bool:
+    """Whether a forward with this flag runs the sparse kernel: there is a
+    merged table whose k segments can be packed (qk_starts) and a kernel built
+    for it (16-bit, d = 64 or 128). Otherwise the flag is accepted and the
+    segment-loop launch runs."""
+    return (bool(sparse_load) and qk_starts is not None and dtype != _FP8
+            and d in (64, 128))
+
+
 def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
         max_logits, qk_starts, max_seqlen_q, softmax_scale, softcap,
         disable_fwd_atomic_reduction, sm_margin, deterministic,
-        pack_gqa=False) -> None:
+        pack_gqa=False, sparse_load=False) -> None:
     """Dense forward into (out, lse): the fp8 entry or the 16-bit one (bf16 or
     fp16 by elem_type) by q.dtype;
     deterministic = fixed merge order, one launch per q-disjoint range group;
     pack_gqa = a workgroup owns a KV head and packs the (token, q head) pairs
-    of its group into its q tiles (where pack_gqa_active)."""
+    of its group into its q tiles (where pack_gqa_active);
+    sparse_load = the k segments of a unique q range are packed into full K/V
+    tiles (where sparse_load_active; every segment must be a full block)."""
     tq, hq, d = q.shape
     tk, hk, _ = k.shape
     pack = pack_gqa_active(pack_gqa, q.dtype, hq, hk)
-    args = (_ffa_lib.MagiFfaFwdPackArgs if pack else _ffa_lib.MagiFfaFwdArgs)(
+    sparse = sparse_load_active(sparse_load, q.dtype, d, qk_starts)
+    args = (_ffa_lib.MagiFfaFwdSparseArgs if sparse else
+            _ffa_lib.MagiFfaFwdPackArgs if pack else _ffa_lib.MagiFfaFwdArgs)(
         q=ptr(q), k=ptr(k), v=ptr(v), out=ptr(out), lse=ptr(lse),
         q_ranges=ptr(q_ranges), k_ranges=ptr(k_ranges),
         attn_type_map=ptr(attn_type_map), locks=ptr(locks),
@@ -175,6 +189,17 @@ def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
     if pack:
         args.pack_gqa = 1
         fn = lib.magi_ffa_fwd_pack
+    if sparse:
+        assert not deterministic, "no deterministic mode over merged tables"
+        # running sum of the segment lengths, on the device: no host sync.
+        # It must outlive the launch, which torch's allocator cannot see:
+        # the same stream reuses the block only behind the kernel.
+        k_cum = torch.zeros(k_ranges.shape[0] + 1, dtype=torch.int32,
+                            device=k_ranges.device)
+        k_cum[1:] = (k_ranges[:, 1] - k_ranges[:, 0]).clamp_min(0).cumsum(0)
+        args.k_cum = ptr(k_cum)
+        args.sparse_load = 1
+        fn = lib.magi_ffa_fwd_sparse
     if deterministic and q_ranges.shape[0] > 1:
         groups = _color_ranges(q_ranges.cpu().tolist())
         launch_per_group(args, q_ranges, k_ranges, attn_type_map,

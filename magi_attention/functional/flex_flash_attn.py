@@ -120,6 +120,7 @@ def _flex_flash_attn_forward(
     max_logits: Optional[torch.Tensor] = None,
     qk_starts: Optional[torch.Tensor] = None,
     pack_gqa: bool = False,
+    sparse_load: bool = False,
     **_unused,
 ) -> tuple[torch.Tensor, AttnForwardMeta]:
     """Dense (range-table) forward into (out, lse). q/k/v are all bf16, all
@@ -128,6 +129,10 @@ def _flex_flash_attn_forward(
     the kernel, and a 16-bit out or out_type must be q's own 16-bit type.
     pack_gqa runs the packed kernel where _ffa_launch.pack_gqa_active says so
     (bf16 / fp16 and hq != hk) and today's launch otherwise.
+    sparse_load runs the sparse kernel where _ffa_launch.sparse_load_active
+    says so (bf16 / fp16, d 64 or 128, qk_starts given) and the segment-loop
+    launch otherwise; every k segment must then be a full block (type 0),
+    which is not checked.
 
     fp16 direct store with a sink: the sink postprocess kernel reads a 16-bit
     out as bf16, so it must never see fp16. That combination therefore runs
@@ -195,6 +200,7 @@ def _flex_flash_attn_forward(
         softcap=softcap,
         disable_fwd_atomic_reduction=disable_fwd_atomic_reduction,
         sm_margin=sm_margin, deterministic=deterministic, pack_gqa=pack_gqa,
+        sparse_load=sparse_load,
     )
     if sink is not None:
         assert out.dtype != torch.float16  # the postprocess reads 16 bits as bf16
@@ -635,6 +641,7 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             deterministic=deterministic, sm_margin=sm_margin,
             max_seqlen_q=max_seqlen_q, max_logits=max_logits,
             qk_starts=fwd_qk_starts, pack_gqa=pack_gqa,
+            sparse_load=sparse_load,
         )
         lse = meta.lse
         # fp8 extension returns bf16 out
@@ -764,6 +771,29 @@ def flex_flash_attn_func(
     usual one. fp8 inputs, index_attn_indices and hq == hk accept the flag
     and run the default launch.
 
+    sparse_load=True (range path, bf16 / fp16, head dims up to 128; requires
+    auto_range_merge=True, RuntimeError otherwise, as in the reference): for
+    block-sparse masks whose k blocks are shorter than the kernel's 64-row K/V
+    stage ("k_range size is small (< 64)"). By default the forward serves the
+    k ranges of a q range one after another, each with whole stages of its
+    own, so a 16-row k block pays for 64 rows and fills half an MFMA tile.
+    With the flag the k ranges of a (unique) q range are laid end to end, in
+    table order, and the kernel gathers 64 rows at a time across them through
+    a row map in LDS: every stage and tile but the last is full. The k ranges
+    of one q range may come in any order and length; one listed twice counts
+    twice, as without the flag. Every slice must be a full block
+    (attn_type_map all 0, as the reference requires): like the two promises
+    of disjoint ranges this one is not checked, since that would take a
+    device sync; the kernel does not read attn_type_map, so a causal slice
+    would be served as a full one. out, lse and max_logits agree with the
+    default launch within rounding (not bit for bit); pack_gqa, softcap, sink,
+    direct store, sm_margin and return_max_logits compose with it, and the
+    backward is the usual one. fp8 inputs and head dims above 128 accept the
+    flag and run the default launch. Whether it pays is measured in
+    profiles/fwd_sparse_load.md: with the direct store it does for k blocks
+    below 64 rows, the crossover lying between 64 and 128; in merge mode only
+    at 16 rows.
+
     Backward stores (range path, bf16 / fp16). By default dq, dk and dv are
     accumulated with atomics in f32 buffers and cast once at the end.
     disable_bwd_dkv_atomic_reduction=True is the promise that the k ranges
@@ -799,6 +829,8 @@ def flex_flash_attn_func(
     assert not (sparse_load and _has_index), (
         "sparse_load and index_attn_indices are mutually exclusive"
     )
+    if sparse_load and not auto_range_merge:
+        raise RuntimeError("When using sparse load, range merge must be enabled.")
     if _has_index:
         assert index_attn_indices.dim() == 3, (
             f"index_attn_indices must be 3D (total_q, num_kv_heads, max_topk), "
@@ -896,7 +928,7 @@ def flex_flash_attn_func(
             max_seqlen_q=max_seqlen_q, max_seqlen_k=max_seqlen_k,
             auto_range_merge=auto_range_merge,
             return_max_logits=return_max_logits,
-            pack_gqa=pack_gqa, cat_gqa=cat_gqa,
+            pack_gqa=pack_gqa, cat_gqa=cat_gqa, sparse_load=sparse_load,
         )
         return out[..., :d], meta
     out, lse, max_logits = FlexFlashAttnFunc.apply(
