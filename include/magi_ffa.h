@@ -75,6 +75,35 @@ typedef struct magi_ffa_fwd_args {
  * out. magi_ffa_fwd_fp8 (raw e4m3 q/k/v) ignores elem_type. */
 int magi_ffa_fwd(const magi_ffa_fwd_args* args);
 
+/* Dense fp8 forward: q/k/v are raw e4m3 bytes, no descale factors; P is
+ * scaled to [0, 256] and packed to e4m3, accumulation is fp32.
+ * magi_ffa_fwd_fp8 is the plain launch: f32 out in merge mode, one k range per
+ * q range, no softcap. It returns -6 for a 16-bit out or
+ * disable_atomic_reduction and -7 for softcap != 0 or qk_starts != NULL.
+ * magi_ffa_fwd_fp8_flex takes the same struct with every member in its
+ * meaning for magi_ffa_fwd (elem_type and cu_margin are not read):
+ *   softcap > 0       score = softcap * tanh(s * scale / softcap); max_logits
+ *                     then holds the softcapped value. 0 = off.
+ *   qk_starts         merged tables: the workgroup of a unique q range walks
+ *                     its k segments in table order and runs one epilogue.
+ *                     Segments may overlap, repeat (a key listed twice counts
+ *                     twice), be empty, or come in any k order. A q block
+ *                     that no segment gives a key leaves out and lse alone.
+ *   disable_atomic_reduction = 1
+ *                     the (unique) q ranges are disjoint: no locks, no read
+ *                     of the previous out / lse, one store per element - bf16
+ *                     rounded to nearest even with out_is_fp32 = 0, f32 with
+ *                     out_is_fp32 = 1. Rows with no key are not written
+ *                     (caller presets out = 0, lse = -inf). locks may be NULL.
+ * With softcap = 0, qk_starts = NULL and merge mode it is magi_ffa_fwd_fp8's
+ * launch, bit for bit. Validation of the flex entry, in this order, all
+ * before any pointer is touched: -1 null struct or q/k/v/out/lse, -2 d not in
+ * {64, 128}, -3 hq % hk != 0, -6 out_is_fp32 == 0 without
+ * disable_atomic_reduction, -7 softcap < 0; then n_ranges <= 0 returns 0
+ * without a launch; -4 merge mode without locks, -5 more than 65535 ranges. */
+int magi_ffa_fwd_fp8(const magi_ffa_fwd_args* args);
+int magi_ffa_fwd_fp8_flex(const magi_ffa_fwd_args* args);
+
 /* pack_gqa (reference flex_flash_attn_func pack_gqa: "pack the Q heads that
  * share one KV head into one q tile"). magi_ffa_fwd runs one workgroup per
  * (q range, q head, block of q rows), a wave owning 32 consecutive tokens of

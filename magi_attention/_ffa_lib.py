@@ -290,6 +290,8 @@ def _try_load() -> ctypes.CDLL | None:
         for name, argtypes in [
             ("magi_ffa_fwd", [ctypes.POINTER(MagiFfaFwdArgs)]),
             ("magi_ffa_fwd_fp8", [ctypes.POINTER(MagiFfaFwdArgs)]),
+            # fp8 with softcap, qk_starts or the direct store (same struct)
+            ("magi_ffa_fwd_fp8_flex", [ctypes.POINTER(MagiFfaFwdArgs)]),
             ("magi_ffa_fwd_pack", [ctypes.POINTER(MagiFfaFwdPackArgs)]),
             ("magi_ffa_fwd_pack_args_size", []),
             ("magi_ffa_fwd_sparse", [ctypes.POINTER(MagiFfaFwdSparseArgs)]),

@@ -17,6 +17,23 @@
 // staged cooperatively (K rows 16B-swizzled for ds_read_b64 A-frags; V into a
 // byte-transposed tile), double-buffered register pipeline. P is packed to
 // fp8 in-register (ONE permlane32_swap per 16-k tile).
+//
+// Variants (template parameters of the one kernel):
+//   HAS_SOFTCAP  t = softcap * log2e * tanh(s * scale / softcap) takes the
+//                place of s * scale * log2e, as in ffa_index_fp8.hip;
+//                max_logits then holds the softcapped value.
+//   ATOMIC       true: lock-guarded read-merge-write into the f32 out (ranges
+//                may overlap). false: the q ranges are disjoint, so every
+//                (row, head) has one owner: no lock, no read of the previous
+//                lse / out, one store per element.
+//   OUT_BF16     direct store only: out is bf16 (round to nearest even) and no
+//                cast pass follows; false = f32.
+// Merged tables (p.qk_starts, run time): a workgroup walks the k segments of
+// its unique q range in the kernel and carries m_run / l_run / acc_o across
+// them, so a q range with many k blocks pays ONE epilogue where one launch
+// row per slice pays a locked read-merge-write of the f32 out per slice.
+// (false, true, false) without qk_starts is the kernel magi_ffa_fwd_fp8 has
+// always launched.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -34,20 +51,27 @@ struct Fp8FwdParams {
   const u8* q;
   const u8* k;
   const u8* v;
-  float* out_f32;
+  float* out_f32;    // used when OUT_BF16 == false
+  bf16_t* out_bf16;  // used when OUT_BF16 == true
   float* lse;
   const int* q_ranges;
   const int* k_ranges;
   const int* attn_type_map;
+  const int* qk_starts;  // auto_range_merge: ri = unique q range, its k
+                         // segments are k_ranges[qk_starts[ri] ..
+                         // qk_starts[ri + 1]) with one attn type each;
+                         // null = one segment per ri
   int* locks;
   float* max_logits;
   int hq, hk, gqa;
   float scale;
+  float softcap;
   long long total_q, total_k;
 };
 
-template <int D>
+template <int D, bool HAS_SOFTCAP, bool ATOMIC, bool OUT_BF16>
 __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
+  static_assert(!(ATOMIC && OUT_BF16), "the merge epilogue needs an f32 out");
   constexpr int DF = D / 16;   // 16-wide d fragments per MFMA chain
   constexpr int DT = D / 32;
   constexpr int ROWB = D;      // bytes per row (1 B per element)
@@ -56,8 +80,10 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
   const int qs = p.q_ranges[2 * ri], qe = p.q_ranges[2 * ri + 1];
   const int m0 = qs + blockIdx.x * FP8_BM;
   if (m0 >= qe) return;
-  const int ks = p.k_ranges[2 * ri], ke = p.k_ranges[2 * ri + 1];
-  const int atype = p.attn_type_map ? p.attn_type_map[ri] : 0;
+  // k segments of this q range: one without qk_starts. A padded trailing
+  // entry of a merged table has qs == qe == 0 and returned above.
+  const int seg0 = p.qk_starts ? p.qk_starts[ri] : ri;
+  const int seg1 = p.qk_starts ? p.qk_starts[ri + 1] : ri + 1;
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -70,24 +96,32 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
   const bool qvalid_any = q0 < qe;
   const int qclamp = qvalid ? qrow : (qe - 1);
 
-  const float sl2 = p.scale * 1.4426950408889634f;
+  const float sl2 =
+      (HAS_SOFTCAP ? p.softcap : p.scale) * 1.4426950408889634f;
+  const float cap_pre = HAS_SOFTCAP ? p.scale / p.softcap : 0.f;
 
-  int n_lo = ks, n_hi = ke;
-  if (ke > ks && q0 < qe) {
-    const int qhiw = min(q0 + 31, qe - 1);
-    if (atype == 1 || atype == 3) n_hi = min(n_hi, qhiw + (ke - qe) + 1);
-    if (atype == 2 || atype == 3) n_lo = max(n_lo, q0 + (ks - qs));
-  } else {
-    n_hi = n_lo;
-  }
-  int b_lo = ks, b_hi = ke;
-  if (ke > ks && m0 < qe) {
-    const int qhib = min(m0 + FP8_BM - 1, qe - 1);
-    if (atype == 1 || atype == 3) b_hi = min(b_hi, qhib + (ke - qe) + 1);
-    if (atype == 2 || atype == 3) b_lo = max(b_lo, m0 + (ks - qs));
-  } else {
-    b_hi = b_lo;
-  }
+  // the current segment, its wave bounds [n_lo, n_hi) and block bounds
+  // [b_lo, b_hi): set by seg_bounds() per segment
+  int ks = 0, ke = 0, atype = 0;
+  int n_lo = 0, n_hi = 0, b_lo = 0, b_hi = 0;
+  auto seg_bounds = [&]() {
+    n_lo = ks, n_hi = ke;
+    if (ke > ks && q0 < qe) {
+      const int qhiw = min(q0 + 31, qe - 1);
+      if (atype == 1 || atype == 3) n_hi = min(n_hi, qhiw + (ke - qe) + 1);
+      if (atype == 2 || atype == 3) n_lo = max(n_lo, q0 + (ks - qs));
+    } else {
+      n_hi = n_lo;
+    }
+    b_lo = ks, b_hi = ke;
+    if (ke > ks && m0 < qe) {
+      const int qhib = min(m0 + FP8_BM - 1, qe - 1);
+      if (atype == 1 || atype == 3) b_hi = min(b_hi, qhib + (ke - qe) + 1);
+      if (atype == 2 || atype == 3) b_lo = max(b_lo, m0 + (ks - qs));
+    } else {
+      b_hi = b_lo;
+    }
+  };
 
   // Q fragments: 8 fp8 bytes per 16-d slice
   long qf[DF];
@@ -160,13 +194,6 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
   };
 
   int cur = 0;
-  if (b_lo < b_hi) {
-    issue_loads(b_lo, kregA, vregA);
-    write_stage(0, kregA, vregA);
-    issue_loads(b_lo + FP8_BN, kregA, vregA);
-  }
-  __syncthreads();
-
   auto iter_body = [&](int n0, auto& kreg_w, auto& vreg_w, auto& kreg_l,
                        auto& vreg_l) {
     const bool has_next = n0 + FP8_BN < b_hi;
@@ -197,7 +224,9 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
     if (interior) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        t[r] = s[r] * sl2;
+        float sv = s[r];
+        if (HAS_SOFTCAP) sv = tanhf(sv * cap_pre);
+        t[r] = sv * sl2;
         mx = fmaxf(mx, t[r]);
       }
     } else {
@@ -207,7 +236,9 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
         bool ok = qvalid && (kk >= n_lo) && (kk < n_hi);
         if (atype == 1 || atype == 3) ok = ok && (kk - qrow <= ke - qe);
         if (atype == 2 || atype == 3) ok = ok && (kk - qrow >= ks - qs);
-        t[r] = ok ? s[r] * sl2 : -INFINITY;
+        float sv = s[r];
+        if (HAS_SOFTCAP) sv = tanhf(sv * cap_pre);
+        t[r] = ok ? sv * sl2 : -INFINITY;
         mx = fmaxf(mx, t[r]);
       }
     }
@@ -236,7 +267,35 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
     cur ^= 1;
   };
 
-  {
+  // Segment loop. m_run, l_run and acc_o run on across the segments: a second
+  // segment is one more stretch of the same online softmax, in table order,
+  // whatever its k rows are (overlapping or repeated ones count again).
+  // Everything that decides a `continue` is block-uniform (ks, ke, atype and
+  // m0), so the barriers below stay matched.
+  bool any_seg = false;
+  for (int seg = seg0; seg < seg1; ++seg) {
+    ks = p.k_ranges[2 * seg];
+    ke = p.k_ranges[2 * seg + 1];
+    atype = p.attn_type_map ? p.attn_type_map[seg] : 0;
+    if (ke <= ks) continue;  // empty segment: no load, no LDS write
+    seg_bounds();
+    if (b_lo >= b_hi) continue;  // the mask leaves this q block no key of it
+    any_seg = true;
+    // Both LDS buffers are free here. Every iteration of the previous
+    // segment ended in a __syncthreads() that follows the wave's last read
+    // of lds_k(cur) / lds_vt(cur), live or not; its last iteration had
+    // has_next == false and wrote no stage. Behind that barrier no wave
+    // reads or writes either buffer until this prologue, so stage 0 may be
+    // overwritten whichever buffer `cur` named last: cur restarts at 0, and
+    // the barrier below publishes the stage before the first fragment read.
+    // The staging registers hold clamped overrun loads of the old segment,
+    // which nothing reads: both sets are reloaded before their next write.
+    cur = 0;
+    issue_loads(b_lo, kregA, vregA);
+    write_stage(0, kregA, vregA);
+    issue_loads(b_lo + FP8_BN, kregA, vregA);
+    __syncthreads();
+
     int n0 = b_lo;
     while (n0 < b_hi) {
       iter_body(n0, kregA, vregA, kregB, vregB);
@@ -246,6 +305,10 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
       n0 += FP8_BN;
     }
   }
+  // No segment staged anything for this q block (block-uniform): the merge
+  // below would rewrite out and lse with their own values, so leave both
+  // untouched and take no lock.
+  if (!any_seg) return;
 
   if (p.max_logits) {
     float ml = m_run * 0.6931471805599453f;  // see bf16 fwd epilogue
@@ -263,66 +326,166 @@ __global__ __launch_bounds__(256, 2) void ffa_fwd_fp8_kernel(Fp8FwdParams p) {
   const float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
   const size_t out_row_pitch = (size_t)p.hq * D;
 
-  const int row_last = min(m0 + FP8_BM, qe) - 1;
-  const int s0 = m0 / LOCK_GRAN, s1 = row_last / LOCK_GRAN;
-  int* lock0 = p.locks + (size_t)s0 * p.hq + h;
-  int* lock1 = p.locks + (size_t)s1 * p.hq + h;
-  if (threadIdx.x == 0) {
-    int expected = 0;
-    while (!__hip_atomic_compare_exchange_strong(
-        lock0, &expected, 1, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED,
-        __HIP_MEMORY_SCOPE_AGENT))
-      expected = 0;
-    if (s1 != s0) {
-      expected = 0;
+  if constexpr (!ATOMIC) {
+    // ---- direct store: disjoint q ranges, one owner per (row, head) ----
+    // Rows with no key keep the host's out = 0 and lse = -inf.
+    if (l_run > 0.f && qvalid && hi == 0)
+      p.lse[(size_t)qrow * p.hq + h] = lse_new;
+    // C/D registers r and r + 1 (r even) are two consecutive q rows of the
+    // lane's column. bf16: lanes 2j and 2j + 1 hold neighbouring columns, so
+    // they trade one value through a DPP quad swap - the even lane then owns
+    // columns (2j, 2j + 1) of row r, the odd lane those of row r + 1 - and
+    // each stores one packed dword, half the stores of a per-element cast.
+    const int odd = lane & 1;
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+      const int src = crow(r, hi);  // crow(r + 1, hi) == src + 1
+      const float il0 = __uint_as_float(
+          __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(inv_l)));
+      const float il1 = __uint_as_float(
+          __builtin_amdgcn_ds_bpermute((src + 1) << 2, __float_as_uint(inv_l)));
+      if constexpr (OUT_BF16) {
+        const int qr = q0 + src + odd;
+        const bool st = qr < qe && (odd ? il1 : il0) > 0.f;
+        const size_t base =
+            (size_t)qr * out_row_pitch + (size_t)h * D + (lo32 & ~1);
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+          const float v0 = acc_o[dt][r] * il0;
+          const float v1 = acc_o[dt][r + 1] * il1;
+          // quad_perm(1, 0, 3, 2): every lane reads its neighbour lane ^ 1;
+          // outside the store predicate, so all lanes take part
+          const float got = __uint_as_float(__builtin_amdgcn_update_dpp(
+              0, __float_as_uint(odd ? v0 : v1), 0xB1, 0xF, 0xF, true));
+          const unsigned pk =
+              odd ? pack_bf16_pair(got, v1) : pack_bf16_pair(v0, got);
+          if (st) *(unsigned*)(p.out_bf16 + base + dt * 32) = pk;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int qr = q0 + src + j;
+          const float ilq = j ? il1 : il0;
+          if (qr >= qe || ilq <= 0.f) continue;
+          const size_t base = (size_t)qr * out_row_pitch + (size_t)h * D;
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt)
+            p.out_f32[base + dt * 32 + lo32] = acc_o[dt][r + j] * ilq;
+        }
+      }
+    }
+  } else {
+    // ---- lock-guarded read-merge-write into the f32 out ----
+    const int row_last = min(m0 + FP8_BM, qe) - 1;
+    const int s0 = m0 / LOCK_GRAN, s1 = row_last / LOCK_GRAN;
+    int* lock0 = p.locks + (size_t)s0 * p.hq + h;
+    int* lock1 = p.locks + (size_t)s1 * p.hq + h;
+    if (threadIdx.x == 0) {
+      int expected = 0;
       while (!__hip_atomic_compare_exchange_strong(
-          lock1, &expected, 1, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED,
+          lock0, &expected, 1, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED,
           __HIP_MEMORY_SCOPE_AGENT))
         expected = 0;
+      if (s1 != s0) {
+        expected = 0;
+        while (!__hip_atomic_compare_exchange_strong(
+            lock1, &expected, 1, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED,
+            __HIP_MEMORY_SCOPE_AGENT))
+          expected = 0;
+      }
     }
-  }
-  __syncthreads();
+    __syncthreads();
 
-  float lse_prev = -INFINITY;
-  if (qvalid) lse_prev = p.lse[(size_t)qrow * p.hq + h];
-  float lse_m;
-  {
-    const float a = fmaxf(lse_prev, lse_new);
-    const float b = fminf(lse_prev, lse_new);
-    lse_m = (a == -INFINITY) ? -INFINITY : a + log1pf(expf(b - a));
-  }
-  const float w_prev = (lse_prev == -INFINITY) ? 0.f : expf(lse_prev - lse_m);
-  const float w_new = (lse_new == -INFINITY) ? 0.f : expf(lse_new - lse_m) * inv_l;
+    float lse_prev = -INFINITY;
+    if (qvalid) lse_prev = p.lse[(size_t)qrow * p.hq + h];
+    float lse_m;
+    {
+      const float a = fmaxf(lse_prev, lse_new);
+      const float b = fminf(lse_prev, lse_new);
+      lse_m = (a == -INFINITY) ? -INFINITY : a + log1pf(expf(b - a));
+    }
+    const float w_prev = (lse_prev == -INFINITY) ? 0.f : expf(lse_prev - lse_m);
+    const float w_new = (lse_new == -INFINITY) ? 0.f : expf(lse_new - lse_m) * inv_l;
 
-  if (qvalid && lse_m != -INFINITY && hi == 0)
-    p.lse[(size_t)qrow * p.hq + h] = lse_m;
+    if (qvalid && lse_m != -INFINITY && hi == 0)
+      p.lse[(size_t)qrow * p.hq + h] = lse_m;
 
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int src = crow(r, hi);
-    const float wp = __uint_as_float(
-        __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(w_prev)));
-    const float wn = __uint_as_float(
-        __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(w_new)));
-    const int qr = q0 + src;
-    if (qr >= qe || (wp == 0.f && wn == 0.f)) continue;
-    const size_t base = (size_t)qr * out_row_pitch + (size_t)h * D;
+    for (int r = 0; r < 16; ++r) {
+      const int src = crow(r, hi);
+      const float wp = __uint_as_float(
+          __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(w_prev)));
+      const float wn = __uint_as_float(
+          __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(w_new)));
+      const int qr = q0 + src;
+      if (qr >= qe || (wp == 0.f && wn == 0.f)) continue;
+      const size_t base = (size_t)qr * out_row_pitch + (size_t)h * D;
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-      float* ptr = p.out_f32 + base + dt * 32 + lo32;
-      const float prev = (wp > 0.f) ? wp * (*ptr) : 0.f;
-      *ptr = prev + wn * acc_o[dt][r];
+      for (int dt = 0; dt < DT; ++dt) {
+        float* ptr = p.out_f32 + base + dt * 32 + lo32;
+        const float prev = (wp > 0.f) ? wp * (*ptr) : 0.f;
+        *ptr = prev + wn * acc_o[dt][r];
+      }
     }
-  }
 
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (s1 != s0)
-      __hip_atomic_store(lock1, 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(lock0, 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (s1 != s0)
+        __hip_atomic_store(lock1, 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(lock0, 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
+}
+
+// Params, grid and dispatch of both entries below, which have validated a:
+// one workgroup per (128-row q block, q range, q head). The variant follows
+// from the struct alone: softcap > 0, disable_atomic_reduction, out_is_fp32.
+static int fp8_fwd_launch(const magi_ffa_fwd_args* a) {
+  Fp8FwdParams p{};
+  p.q = (const u8*)a->q;
+  p.k = (const u8*)a->k;
+  p.v = (const u8*)a->v;
+  p.out_f32 = (float*)a->out;
+  p.out_bf16 = (bf16_t*)a->out;
+  p.lse = a->lse;
+  p.q_ranges = a->q_ranges;
+  p.k_ranges = a->k_ranges;
+  p.attn_type_map = a->attn_type_map;
+  p.qk_starts = a->qk_starts;
+  p.locks = a->locks;
+  p.max_logits = a->max_logits;
+  p.hq = a->hq;
+  p.hk = a->hk;
+  p.gqa = a->hq / a->hk;
+  p.scale = a->softmax_scale;
+  p.softcap = a->softcap;
+  p.total_q = a->total_q;
+  p.total_k = a->total_k;
+
+  const int mblocks = (a->max_seqlen_q + FP8_BM - 1) / FP8_BM;
+  const dim3 grid(mblocks, (unsigned)a->n_ranges, a->hq), block(256);
+  const hipStream_t s = (hipStream_t)a->stream;
+  auto go = [&](auto D, auto SC, auto AT, auto OB) {
+    hipLaunchKernelGGL((ffa_fwd_fp8_kernel<D(), SC(), AT(), OB()>), grid,
+                       block, 0, s, p);
+  };
+  auto with_sc = [&](auto D, auto SC) {
+    if (!a->disable_atomic_reduction)
+      go(D, SC, std::true_type{}, std::false_type{});
+    else if (a->out_is_fp32)
+      go(D, SC, std::false_type{}, std::false_type{});
+    else
+      go(D, SC, std::false_type{}, std::true_type{});
+  };
+  auto with_d = [&](auto D) {
+    if (a->softcap > 0.f) with_sc(D, std::true_type{});
+    else with_sc(D, std::false_type{});
+  };
+  if (a->d == 128) with_d(std::integral_constant<int, 128>{});
+  else with_d(std::integral_constant<int, 64>{});
+  return (int)hipGetLastError();
 }
 
 extern "C" int magi_ffa_fwd_fp8(const magi_ffa_fwd_args* a) {
@@ -334,33 +497,22 @@ extern "C" int magi_ffa_fwd_fp8(const magi_ffa_fwd_args* a) {
   if (a->n_ranges <= 0) return 0;
   if (!a->locks) return -4;
   if (a->n_ranges > 65535) return -5;
-
-  Fp8FwdParams p{};
-  p.q = (const u8*)a->q;
-  p.k = (const u8*)a->k;
-  p.v = (const u8*)a->v;
-  p.out_f32 = (float*)a->out;
-  p.lse = a->lse;
-  p.q_ranges = a->q_ranges;
-  p.k_ranges = a->k_ranges;
-  p.attn_type_map = a->attn_type_map;
-  p.locks = a->locks;
-  p.max_logits = a->max_logits;
-  // fp8 fwd: auto_range_merge segments not supported yet
+  // merged tables go through magi_ffa_fwd_fp8_flex
   if (a->qk_starts) return -7;
-  p.hq = a->hq;
-  p.hk = a->hk;
-  p.gqa = a->hq / a->hk;
-  p.scale = a->softmax_scale;
-  p.total_q = a->total_q;
-  p.total_k = a->total_k;
+  return fp8_fwd_launch(a);
+}
 
-  const int mblocks = (a->max_seqlen_q + FP8_BM - 1) / FP8_BM;
-  dim3 grid(mblocks, (unsigned)a->n_ranges, a->hq), block(256);
-  hipStream_t s = (hipStream_t)a->stream;
-  if (a->d == 128)
-    hipLaunchKernelGGL((ffa_fwd_fp8_kernel<128>), grid, block, 0, s, p);
-  else
-    hipLaunchKernelGGL((ffa_fwd_fp8_kernel<64>), grid, block, 0, s, p);
-  return (int)hipGetLastError();
+// The full launch surface of the 16-bit entry for fp8 inputs: softcap,
+// qk_starts (merged tables) and the direct store into a bf16 or f32 out.
+// Codes and order: magi_ffa.h.
+extern "C" int magi_ffa_fwd_fp8_flex(const magi_ffa_fwd_args* a) {
+  if (!a || !a->q || !a->k || !a->v || !a->out || !a->lse) return -1;
+  if (a->d != 128 && a->d != 64) return -2;
+  if (a->hq % a->hk != 0) return -3;
+  if (!a->out_is_fp32 && !a->disable_atomic_reduction) return -6;
+  if (a->softcap < 0.f) return -7;
+  if (a->n_ranges <= 0) return 0;
+  if (!a->disable_atomic_reduction && !a->locks) return -4;
+  if (a->n_ranges > 65535) return -5;
+  return fp8_fwd_launch(a);
 }

@@ -155,12 +155,22 @@ def sparse_load_active(sparse_load, dtype: torch.dtype, d: int,
             and d in (64, 128))
 
 
+def fp8_flex_active(dtype: torch.dtype, softcap, qk_starts,
+                    disable_fwd_atomic_reduction) -> bool:
+    """Whether an fp8 forward goes to magi_ffa_fwd_fp8_flex: it asks for
+    something the plain fp8 entry refuses (softcap, a merged table, the direct
+    store). Every other fp8 call keeps the plain entry; 16-bit calls never
+    come here."""
+    return dtype == _FP8 and (softcap != 0 or qk_starts is not None
+                              or bool(disable_fwd_atomic_reduction))
+
+
 def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
         max_logits, qk_starts, max_seqlen_q, softmax_scale, softcap,
         disable_fwd_atomic_reduction, sm_margin, deterministic,
         pack_gqa=False, sparse_load=False) -> None:
-    """Dense forward into (out, lse): the fp8 entry or the 16-bit one (bf16 or
-    fp16 by elem_type) by q.dtype;
+    """Dense forward into (out, lse): an fp8 entry (the flex one where
+    fp8_flex_active) or the 16-bit one (bf16 or fp16 by elem_type) by q.dtype;
     deterministic = fixed merge order, one launch per q-disjoint range group;
     pack_gqa = a workgroup owns a KV head and packs the (token, q head) pairs
     of its group into its q tiles (where pack_gqa_active);
@@ -186,6 +196,12 @@ def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
     )
     lib = _ffa_lib.lib()
     fn = lib.magi_ffa_fwd_fp8 if q.dtype == _FP8 else lib.magi_ffa_fwd
+    if fp8_flex_active(q.dtype, softcap, qk_starts,
+                       disable_fwd_atomic_reduction):
+        assert not (deterministic and qk_starts is not None), (
+            "no deterministic mode over merged tables"
+        )
+        fn = lib.magi_ffa_fwd_fp8_flex
     if pack:
         args.pack_gqa = 1
         fn = lib.magi_ffa_fwd_pack

@@ -125,13 +125,17 @@ def _flex_flash_attn_forward(
 ) -> tuple[torch.Tensor, AttnForwardMeta]:
     """Dense (range-table) forward into (out, lse). q/k/v are all bf16, all
     fp16 or all fp8-e4m3. In merge mode out is an f32 accumulator; with
-    disable_fwd_atomic_reduction it defaults to q's dtype, stored directly by
-    the kernel, and a 16-bit out or out_type must be q's own 16-bit type.
+    disable_fwd_atomic_reduction it defaults to q's dtype (bf16 for fp8
+    inputs), stored directly by the kernel, and a 16-bit out or out_type must
+    be q's own 16-bit type (bf16 for fp8).
+    fp8 takes softcap, qk_starts and the direct store like the 16-bit types
+    (_ffa_launch.fp8_flex_active picks the entry); d is 64 or 128.
     pack_gqa runs the packed kernel where _ffa_launch.pack_gqa_active says so
     (bf16 / fp16 and hq != hk) and today's launch otherwise.
     sparse_load runs the sparse kernel where _ffa_launch.sparse_load_active
     says so (bf16 / fp16, d 64 or 128, qk_starts given) and the segment-loop
-    launch otherwise; every k segment must then be a full block (type 0),
+    launch otherwise - for fp8 that is the fp8 kernel's own segment loop;
+    with the sparse kernel every k segment must be a full block (type 0),
     which is not checked.
 
     fp16 direct store with a sink: the sink postprocess kernel reads a 16-bit
@@ -162,7 +166,8 @@ def _flex_flash_attn_forward(
     tq, hq, d = q.shape
 
     dtype = out.dtype if out is not None else out_type or (
-        q.dtype if disable_fwd_atomic_reduction else torch.float32
+        (torch.bfloat16 if is_fp8 else q.dtype)
+        if disable_fwd_atomic_reduction else torch.float32
     )
     # fp16 direct store + sink: f32 out through the sink, one cast at the end
     via_f32 = (sink is not None and disable_fwd_atomic_reduction
@@ -186,13 +191,10 @@ def _flex_flash_attn_forward(
     if max_seqlen_q is None:
         max_seqlen_q = _max_seqlen_of(q_ranges)
 
-    if is_fp8:
-        assert not disable_fwd_atomic_reduction and out_is_fp32
     if qk_starts is not None:
         assert not deterministic, (
             "deterministic + auto_range_merge lands in a later round"
         )
-        assert not is_fp8, "fp8 + auto_range_merge lands in a later round"
     _ffa_launch.fwd(
         q, k, v, out, lse, q_ranges, k_ranges, attn_type_map,
         locks=locks, max_logits=max_logits, qk_starts=qk_starts,
@@ -757,6 +759,19 @@ def flex_flash_attn_func(
     fp16 before their MFMAs and accumulate in fp32. Mixed 16-bit dtypes are
     rejected; index_attn_indices stays bf16 / fp8 only.
 
+    On the range path q/k/v may be all float8_e4m3fn as well (head dim 64 or
+    128, raw e4m3, no descale factors): the fp8 forward kernel, bf16 out, f32
+    lse, bf16-upcast backward with f32 accumulators, fp8 gradients. softcap,
+    disable_fwd_atomic_reduction (out is stored once, as bf16, with no lock,
+    no f32 buffer and no cast pass), sink, deterministic and
+    return_max_logits (the softcapped logit under softcap) apply as for bf16.
+    auto_range_merge=True with fp8 is still refused by this function (and
+    with it sparse_load, which needs it), although the fp8 kernel serves
+    merged tables - it walks the k segments of a unique q range itself and
+    merges once: FlexFlashAttnFunc.apply, which this function ends in, and
+    the context-parallel runtime under MAGI_ATTENTION_AUTO_RANGE_MERGE run
+    them.
+
     pack_gqa=True (range path, bf16 / fp16, it acts when hq != hk): a forward
     workgroup owns a KV head and fills its 32-row q tiles with the (token,
     q head) pairs of the GQA group, heads minor, staging K/V once for the
@@ -789,7 +804,9 @@ def flex_flash_attn_func(
     default launch within rounding (not bit for bit); pack_gqa, softcap, sink,
     direct store, sm_margin and return_max_logits compose with it, and the
     backward is the usual one. fp8 inputs and head dims above 128 accept the
-    flag and run the default launch. Whether it pays is measured in
+    flag and run the default launch, which for fp8 (past this function's
+    refusal of fp8 + auto_range_merge, see above) is the fp8 kernel's segment
+    loop over the merged table. Whether it pays is measured in
     profiles/fwd_sparse_load.md: with the direct store it does for k blocks
     below 64 rows, the crossover lying between 64 and 128; in merge mode only
     at 16 rows.
@@ -831,6 +848,14 @@ def flex_flash_attn_func(
     )
     if sparse_load and not auto_range_merge:
         raise RuntimeError("When using sparse load, range merge must be enabled.")
+    # This function's own refusal is existing, tested behaviour and stays. The
+    # fp8 kernel serves merged tables: FlexFlashAttnFunc, called directly, and
+    # the context-parallel runtime run them.
+    assert not (_has_ranges and auto_range_merge
+                and q.dtype == torch.float8_e4m3fn), (
+        "fp8 + auto_range_merge is not switched on in flex_flash_attn_func; "
+        "FlexFlashAttnFunc.apply and the context-parallel runtime take it"
+    )
     if _has_index:
         assert index_attn_indices.dim() == 3, (
             f"index_attn_indices must be 3D (total_q, num_kv_heads, max_topk), "
