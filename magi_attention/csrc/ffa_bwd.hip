@@ -658,30 +658,66 @@ void ffa_bwd_dkv_kernel(BwdParams<ET> p) {
           pipe_mm(q_base, Tr::afrag(dsv, 0), Tr::afrag(dsv, 1),
                   acc_dk);
         } else {
-          // MODE 0 (fused dK+dV): INTERLEAVE the two independent MFMA
-          // streams — each fragment load's LDS latency is covered by the
-          // OTHER stream's in-flight MFMA, which a single serialized stream
-          // cannot do (the allocator coalesces any explicit double-buffer
-          // at this register pressure).
+          // MODE 0 (fused dK+dV): the two MFMA streams alternate, step
+          // j = 4 * dt + {dV rows 0-15, dK rows 0-15, dV rows 16-31,
+          // dK rows 16-31}, so each accumulator still takes its two
+          // k-halves in order with dt ascending. Interleaving alone does
+          // not hide the LDS latency: left to itself the scheduler issues
+          // every tr16 pair directly in front of its own MFMA and the wave
+          // parks on lgkmcnt(0) sixteen times per subtile. So the pair of
+          // step j+1 is issued before the MFMA of step j, across the dV/dK
+          // alternation and across dt, and the sched_group_barriers hold
+          // that order (as in the dQ kernel); each MFMA then waits with a
+          // counted lgkmcnt for its own fragment only. The pipeline lives
+          // inside this subtile: every read is of the image the current
+          // pipe_barrier retired, and a skipped subtile issues none.
           vec8 pa0 = Tr::afrag(pv, 0);
           vec8 pa1 = Tr::afrag(pv, 1);
           vec8 da0 = Tr::afrag(dsv, 0);
           vec8 da1 = Tr::afrag(dsv, 1);
+          // The look-ahead fragment costs 4 more live registers, and the
+          // D=128 8-wave build is at the 256 cap. Written as in pipe_mm, the
+          // 16 per-lane addresses (dt x row group x two reads) are loop
+          // invariants that the compiler keeps in 16 registers, two of
+          // which it then reloads from scratch in front of the first read,
+          // behind a vmcnt(0) that also waits out the Q/dO prefetch. All 16
+          // derive from two lane values: row r + 4 swizzles like r with bit
+          // 2 of the XOR flipped (row0 has bit 2 clear), row r + 16 like r
+          // (16 is a multiple of the swizzle period), and dt only flips
+          // bits of the XOR. pin_vgpr makes the two opaque here, inside the
+          // loop, so the addresses are rebuilt per step (an XOR and an add
+          // under the running MFMA) and the row constants fold into the
+          // read's immediate offset: 2 live registers in place of 16.
+          static_assert(16 % (SW32M + 1) == 0, "rows r, r + 16 swizzle alike");
+          int rsel = rb0;                          // row0 * ROWB + lane8
+          int xsel = (16 * qhalf * 2) ^ sw0;       // d column 0, swizzled
+          pin_vgpr(rsel);
+          pin_vgpr(xsel);
+          auto bfrag = [&](int j) -> vec8 {
+            const int tbase = ((j & 1) ? q_base : do_base) +
+                              ((j & 2) ? 16 * ROWB : 0);
+            const int x0 = xsel ^ ((j >> 2) * 64);
+            const int x1 = x0 ^ ((4 & SW32M) << 5);
+            return Tr::tr16(tbase + rsel + x0,
+                            tbase + 4 * ROWB + rsel + x1);
+          };
+          vec8 bcur = bfrag(0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read x2
 #pragma unroll
-          for (int dt = 0; dt < DT; ++dt) {
-            const int dcol = (dt * 32 + 16 * qhalf) * 2;
-            vec8 bdo = Tr::tr16(do_base + rb0 + (dcol ^ sw0),
-                                   do_base + rb1 + (dcol ^ sw1));
-            acc_dv[dt] = Tr::mfma(pa0, bdo, acc_dv[dt]);
-            vec8 bq = Tr::tr16(q_base + rb0 + (dcol ^ sw0),
-                                  q_base + rb1 + (dcol ^ sw1));
-            acc_dk[dt] = Tr::mfma(da0, bq, acc_dk[dt]);
-            vec8 bdo1 = Tr::tr16(do_base + rb2 + (dcol ^ sw2),
-                                    do_base + rb3 + (dcol ^ sw3));
-            acc_dv[dt] = Tr::mfma(pa1, bdo1, acc_dv[dt]);
-            vec8 bq1 = Tr::tr16(q_base + rb2 + (dcol ^ sw2),
-                                   q_base + rb3 + (dcol ^ sw3));
-            acc_dk[dt] = Tr::mfma(da1, bq1, acc_dk[dt]);
+          for (int j = 0; j < 4 * DT; ++j) {
+            vec8 bnext = bcur;
+            if (j + 1 < 4 * DT) {
+              bnext = bfrag(j + 1);
+              __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            }
+            const vec8 a = (j & 1) ? ((j & 2) ? da1 : da0)
+                                   : ((j & 2) ? pa1 : pa0);
+            if (j & 1)
+              acc_dk[j >> 2] = Tr::mfma(a, bcur, acc_dk[j >> 2]);
+            else
+              acc_dv[j >> 2] = Tr::mfma(a, bcur, acc_dv[j >> 2]);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA x1
+            bcur = bnext;
           }
         }
       }
