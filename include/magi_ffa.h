@@ -330,6 +330,57 @@ int magi_ffa_bwd_dv_cat(const magi_ffa_bwd_cat_args* args);
 int magi_ffa_bwd_dk_cat(const magi_ffa_bwd_cat_args* args);
 int magi_ffa_bwd_cat_args_size(void);
 
+/* sparse_load for the dq pass (the backward twin of magi_ffa_fwd_sparse).
+ * Under seg_starts magi_ffa_bwd_dq serves a unique q range's k segments one
+ * after another, each with whole 64-row K/V stages of its own, a ring
+ * restart, a drain and a barrier: with k blocks of 16 or 32 rows most of every
+ * stage and MFMA tile is padding. The switch rides behind an embedded copy of
+ * the cat struct (a pointer to the new one passes to the older entries; the
+ * dkv / dv / dk passes take &args->cat and know nothing of the new members):
+ *   sparse_load 0: exactly magi_ffa_bwd_dq_direct(&cat.direct), bit for bit;
+ *             k_cum and reserved are not read.
+ *             1: the k rows of unique q range ri are one virtual axis, the
+ *             segments k_ranges[seg_starts[ri] .. seg_starts[ri + 1]) laid
+ *             end to end in table order: L = sum of (ke - ks) rows. Empty
+ *             segments add nothing, segments may come in any k order and
+ *             length (1 included), and a segment listed twice counts twice,
+ *             as it does with sparse_load = 0. The k loop stages 64 virtual
+ *             rows at a time through a row map the workgroup keeps in LDS
+ *             (2048 rows; longer axes are walked in chunks), so every K/V
+ *             stage and every MFMA tile but a chunk's last is full.
+ *             Every segment is a full block (type 0): attn_type_map is NOT
+ *             read, and the caller vouches for it as it does for disjoint
+ *             ranges. seg_starts is required. A range with L = 0 leaves its
+ *             dq rows untouched. dq has the usual layout and meaning and is
+ *             within rounding of the sparse_load = 0 result, not bit-equal
+ *             (the tile composition changes). cat.direct.dq_is_16bit,
+ *             softcap, both element types, GQA and cu_margin compose with
+ *             it; cat.cat_gqa and cat.reserved belong to the dkv passes and
+ *             are not read. Built for d = 64 and 128; d = 192 runs the
+ *             sparse_load = 0 launch (k_cum unread) and is not an error. The
+ *             launcher picks 4 or 8 waves as magi_ffa_bwd_dq does
+ *             (max_seqlen_k against MAGI_BWD_DQ_BIGSEQ).
+ *   k_cum     int32 [n_segments + 1], n_segments = seg_starts[n_ranges], as
+ *             magi_ffa_fwd_sparse_args.k_cum: k_cum[0] = 0, k_cum[s + 1] =
+ *             k_cum[s] + max(ke_s - ks_s, 0) over k_ranges (a device cumsum;
+ *             no host sync). A k_cum that disagrees with k_ranges gives wrong
+ *             results; mapped rows are clamped to [0, total_k).
+ *   reserved  must be 0.
+ * Validation with sparse_load = 1, in this order, all before any HIP call:
+ * -1 null pointer, -2 head dim, -3 hq % hk != 0, -9 elem_type, -14 reserved
+ * != 0, -15 seg_starts == NULL, -1 k_cum == NULL; then n_ranges <= 0 returns
+ * 0 without a launch; -5 more than 65535 ranges.
+ * magi_ffa_bwd_sparse_args_size is sizeof of the struct as compiled. */
+typedef struct magi_ffa_bwd_sparse_args {
+  magi_ffa_bwd_cat_args cat;
+  const int32_t* k_cum;     /* int32 [n_segments + 1], as magi_ffa_fwd_sparse */
+  int32_t sparse_load;
+  int32_t reserved;         /* must be 0 */
+} magi_ffa_bwd_sparse_args;
+
+int magi_ffa_bwd_dq_sparse(const magi_ffa_bwd_sparse_args* args);
+int magi_ffa_bwd_sparse_args_size(void);
+
 /* ------------------------------------------------------------------ *
  * Range row ops (reference common/range_op/_range_*.py — Triton there,
  * hand-written HIP here; pack/unpack engine of the group collectives). *

@@ -144,6 +144,21 @@ class MagiFfaBwdCatArgs(MagiFfaBwdDirectArgs):
     ]
 
 
+class MagiFfaBwdSparseArgs(MagiFfaBwdCatArgs):
+    """mirrors magi_ffa_bwd_sparse_args: magi_ffa_bwd_cat_args embedded first,
+    then the sparse_load switch of magi_ffa_bwd_dq_sparse and its table. An
+    instance also passes as the three structs it starts with."""
+
+    _fields_ = [
+        # int32 [n_segments + 1]: running sum of the k segment lengths
+        ("k_cum", ctypes.c_void_p),
+        # 1: the dq pass packs a unique q range's k segments into full K/V
+        # tiles (needs seg_starts, all segments full); 0: the _direct launch
+        ("sparse_load", ctypes.c_int32),
+        ("sparse_reserved", ctypes.c_int32),  # `reserved` in C; must be 0
+    ]
+
+
 class MagiRangeOpArgs(ctypes.Structure):
     _fields_ = [
         ("input", ctypes.c_void_p),
@@ -314,6 +329,8 @@ def _try_load() -> ctypes.CDLL | None:
             ("magi_ffa_bwd_dv_cat", [ctypes.POINTER(MagiFfaBwdCatArgs)]),
             ("magi_ffa_bwd_dk_cat", [ctypes.POINTER(MagiFfaBwdCatArgs)]),
             ("magi_ffa_bwd_cat_args_size", []),
+            ("magi_ffa_bwd_dq_sparse", [ctypes.POINTER(MagiFfaBwdSparseArgs)]),
+            ("magi_ffa_bwd_sparse_args_size", []),
             ("magi_range_gather", [ctypes.POINTER(MagiRangeOpArgs)]),
             ("magi_range_reduce", [ctypes.POINTER(MagiRangeOpArgs)]),
             ("magi_correct_out_lse", [ctypes.POINTER(MagiCorrectArgs)]),
@@ -351,6 +368,7 @@ def _try_load() -> ctypes.CDLL | None:
             (MagiFfaFwdSparseArgs, lib.magi_ffa_fwd_sparse_args_size()),
             (MagiFfaBwdDirectArgs, lib.magi_ffa_bwd_direct_args_size()),
             (MagiFfaBwdCatArgs, lib.magi_ffa_bwd_cat_args_size()),
+            (MagiFfaBwdSparseArgs, lib.magi_ffa_bwd_sparse_args_size()),
         ]:
             if ctypes.sizeof(cls) != size:
                 raise RuntimeError(

@@ -33,6 +33,7 @@ SOURCES = [
 # not compiled on their own, but part of the build stamp
 HEADERS = [
     CSRC / "ffa_device.h",
+    CSRC / "ffa_bwd_dq_body.h",
     PKG.parent / "include" / "magi_ffa.h",
 ]
 

@@ -1,7 +1,7 @@
 // ffa_device.h — code shared by the FFA kernels (gfx950, wave64); the device
 // helpers are force-inlined. Sections, with the files that use them:
-//   pipeline    pipe_barrier, glds16_untracked, drain_vm, pin_vgpr
-//               (ffa_fwd, ffa_bwd)
+//   pipeline    pipe_barrier, glds16_untracked, drain_vm, pin_vgpr,
+//               SPARSE_MAP_ROWS (ffa_fwd, ffa_bwd)
 //   lanes       warp_xor32 (all kernels)
 //   index rows  index_valid_count (index forwards and backward),
 //               index_sink_lse, index_sink_fold, head_atomic_max
@@ -71,6 +71,13 @@ template <class T>
 DEV_INLINE void pin_vgpr(T& x) {
   asm volatile("" : "+v"(x));
 }
+
+// SPARSE (sparse_load; the forward and the dQ pass): rows of the
+// virtual-k-row -> global-K-row map a workgroup keeps in LDS behind the
+// staging ring (8 KB). Longer virtual axes are walked in chunks of this many
+// rows. Sized so that the 4-wave D=128 kernels (64 KB ring) still fit two
+// workgroups in a CU's 160 KB.
+#define SPARSE_MAP_ROWS 2048
 
 DEV_INLINE float warp_xor32(float v) { return __shfl_xor(v, 32, 64); }
 

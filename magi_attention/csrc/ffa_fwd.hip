@@ -38,11 +38,6 @@
 #define FFA_BM 128   // q rows per workgroup (4 waves x 32)
 #define FFA_BN 32    // k rows per inner tile
 #define LOCK_GRAN 128
-// SPARSE (sparse_load): rows of the virtual-k-row -> global-K-row map a
-// workgroup keeps in LDS behind the staging ring (8 KB). Longer virtual axes
-// are walked in chunks of this many rows. Sized so that the 4-wave D=128
-// kernel (64 KB ring) still fits two workgroups in a CU's 160 KB.
-#define SPARSE_MAP_ROWS 2048
 
 // ET: element type of q/k/v and of a 16-bit out, bf16_t or f16_t
 template <class ET>

@@ -229,12 +229,14 @@ def bwd_args(dout, out, dpsum, *, q=None, k=None, v=None, lse=None,
              dq=None, dk=None, dv=None, q_ranges=None, k_ranges=None,
              attn_type_map=None, max_seqlen_k=0, softmax_scale=0.0,
              softcap=0.0, sm_margin=0,
-             cat_gqa=False) -> _ffa_lib.MagiFfaBwdCatArgs:
+             cat_gqa=False) -> _ffa_lib.MagiFfaBwdSparseArgs:
     """The backward argument struct. (dout, out, dpsum) are all the dpsum
     preprocess reads; the dq/dk/dv passes need every member. The tensors must
     be contiguous and outlive the launches. dout's dtype (bf16 or fp16) is the
     element type of q/k/v too, and of a 16-bit out. The struct is the one of
-    the magi_ffa_bwd_*_cat entries (it passes as the _direct and the plain one
+    magi_ffa_bwd_dq_sparse, its switch off (run_bwd_passes sets it), which
+    starts with the one of the magi_ffa_bwd_*_cat entries (it passes as the
+    _direct and the plain one
     too); the dtypes of dq and of dk/dv pick each pass's epilogue there: f32 =
     atomic accumulation, the element type = direct store (the caller vouches
     for disjoint ranges). cat_gqa: a dK/dV workgroup owns a KV head and walks
@@ -250,7 +252,7 @@ def bwd_args(dout, out, dpsum, *, q=None, k=None, v=None, lse=None,
         )
         return int(bool(dtypes) and torch.float32 not in dtypes)
 
-    return _ffa_lib.MagiFfaBwdCatArgs(
+    return _ffa_lib.MagiFfaBwdSparseArgs(
         dout=ptr(dout), q=ptr(q), k=ptr(k), v=ptr(v), out=ptr(out),
         lse=ptr(lse), dq=ptr(dq), dk=ptr(dk), dv=ptr(dv), dpsum=ptr(dpsum),
         q_ranges=ptr(q_ranges), k_ranges=ptr(k_ranges),
@@ -311,14 +313,42 @@ def run_bwd_deterministic(args, q_ranges, k_ranges, attn_type_map) -> None:
                      [(bwd_dq, "bwd_dq[det]", q_groups, 1)] + dkv)
 
 
-def run_bwd_passes(args, device, dq_tables=None, dkv_tables=None) -> None:
+def bwd_sparse_load_active(sparse_load, dtype: torch.dtype, d: int,
+                           dq_tables) -> bool:
+    """Whether a backward with this flag runs the sparse dQ kernel: there are
+    merged dq tables whose k segments can be packed and a kernel built for
+    them (16-bit, d = 64 or 128). Otherwise the flag is accepted and the
+    segment-loop dQ pass runs. The dK/dV passes never look at it."""
+    return (bool(sparse_load) and dq_tables is not None
+            and dtype in (torch.bfloat16, torch.float16) and d in (64, 128))
+
+
+def run_bwd_passes(args, device, dq_tables=None, dkv_tables=None,
+                   sparse_load=False) -> None:
     """Launch the independent backward passes (dq / fused-dkv by default;
     dq / dv / dk with MAGI_BWD_SPLIT_DKV=1) on two streams so their waves
     co-schedule across the chip. dq_tables / dkv_tables override the range
     tables per pass for auto_range_merge: (ranges_outer, ranges_inner,
-    attn_type_map, seg_starts) — outer = the pass's OWN loop dim."""
+    attn_type_map, seg_starts) — outer = the pass's OWN loop dim.
+    sparse_load (the caller has applied bwd_sparse_load_active): the dq launch
+    alone goes through magi_ffa_bwd_dq_sparse, which packs the k segments of a
+    unique q range into full K/V tiles; every slice must be a full block."""
     bwd_dq, bwd_dkv, bwd_dv, bwd_dk = _bwd_entries(args)
     main = torch.cuda.current_stream(device)
+    k_cum = None
+    if sparse_load:
+        assert dq_tables is not None, "sparse_load packs a merged table"
+        assert isinstance(args, _ffa_lib.MagiFfaBwdSparseArgs)
+        # running sum of the k segment lengths, on the device: no host sync.
+        # Built on the main stream BEFORE the side stream takes its wait on
+        # it, and referenced until main has waited for side again: the dq
+        # kernel may run on the side stream, which torch's allocator cannot
+        # see, like the merged tables the caller holds.
+        inner = dq_tables[1]
+        k_cum = torch.zeros(inner.shape[0] + 1, dtype=torch.int32,
+                            device=inner.device)
+        k_cum[1:] = (inner[:, 1] - inner[:, 0]).clamp_min(0).cumsum(0)
+        bwd_dq = _ffa_lib.lib().magi_ffa_bwd_dq_sparse
     cosched = env.is_bwd_cosched()
     side = _get_side_stream(device) if cosched else main
     if cosched:
@@ -336,7 +366,11 @@ def run_bwd_passes(args, device, dq_tables=None, dkv_tables=None) -> None:
 
     args.stream = ctypes.c_void_p(side.cuda_stream)
     set_tables(dq_tables, True)
+    if k_cum is not None:
+        args.k_cum, args.sparse_load = ptr(k_cum), 1
     check(bwd_dq(args), "magi_ffa_bwd_dq")
+    if k_cum is not None:  # the dkv entries do not read them; leave none set
+        args.k_cum, args.sparse_load = None, 0
     args.stream = ctypes.c_void_p(main.cuda_stream)
     set_tables(dkv_tables, False)
     if env.is_bwd_split_dkv(args.max_seqlen_k, args.d):
@@ -346,17 +380,20 @@ def run_bwd_passes(args, device, dq_tables=None, dkv_tables=None) -> None:
         check(bwd_dkv(args), "magi_ffa_bwd_dkv")
     if cosched:
         main.wait_stream(side)
+    del k_cum  # main is ordered behind the dq kernel from here on
 
 
 def run_bwd(args, q_ranges, k_ranges, attn_type_map, device, *,
-            deterministic: bool, merged=None) -> None:
+            deterministic: bool, merged=None, sparse_load=False) -> None:
     """The dq/dk/dv passes over a filled, preprocessed args; merged =
-    (dq_tables, dkv_tables) of run_bwd_passes under auto_range_merge."""
+    (dq_tables, dkv_tables) of run_bwd_passes under auto_range_merge, and
+    sparse_load its switch (merged tables only, which deterministic mode
+    refuses, so it never meets the flag)."""
     if deterministic:
         assert merged is None, "no deterministic mode over merged tables"
         run_bwd_deterministic(args, q_ranges, k_ranges, attn_type_map)
     else:
-        run_bwd_passes(args, device, *(merged or ()))
+        run_bwd_passes(args, device, *(merged or ()), sparse_load=sparse_load)
 
 
 # ---------------- index attention ----------------

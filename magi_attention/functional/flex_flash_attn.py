@@ -475,6 +475,7 @@ def _flex_flash_attn_backward(
     auto_range_merge: bool = False,
     disable_bwd_dq_atomic_reduction: bool = False,
     cat_gqa: bool = False,
+    sparse_load: bool = False,
     **_unused,
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """Dense (range-table) backward; returns (dq, dk, dv, dsink). q/k/v are
@@ -506,6 +507,15 @@ def _flex_flash_attn_backward(
     GQA too. It composes with auto_range_merge, deterministic (one launch per
     k-disjoint group: no per-head sub-launches), the split and the fused dK/dV
     passes, softcap, sink and padded head dims. The dq pass is not touched.
+
+    sparse_load takes effect together with auto_range_merge, where
+    _ffa_launch.bwd_sparse_load_active says so (bf16 / fp16, head dim 64 or
+    128; otherwise the flag is accepted and the usual pass runs): the dQ
+    kernel lays the k ranges of a unique q range end to end and gathers full
+    64-row K/V stages across them, where the usual pass stages each k range on
+    its own. Every slice must be a full block: the kernel does not read
+    attn_type_map. dq agrees with the usual pass within rounding, not bit for
+    bit; the dK/dV passes are untouched.
 
     disable_bwd_dq_atomic_reduction is the same for dq and disjoint q ranges
     (dq_type, default q.dtype). The reference has no such flag, its dQ is not
@@ -595,6 +605,8 @@ def _flex_flash_attn_backward(
     _ffa_launch.run_bwd(
         args, q_ranges, k_ranges, attn_type_map, q.device,
         deterministic=deterministic, merged=merged,
+        sparse_load=_ffa_launch.bwd_sparse_load_active(
+            sparse_load, q.dtype, q.shape[-1], merged and merged[0]),
     )
     return dq, dk, dv, dsink
 
@@ -612,13 +624,17 @@ class FlexFlashAttnFunc(torch.autograd.Function):
         auto_range_merge=False, swap_ab=False, pack_gqa=False, cat_gqa=False,
         sparse_load=False, index_attn=False, swap_bwd_qk_loop=False,
         return_max_logits=False, index_attn_indices_2d=None,
-        index_attn_max_topk=0, max_seqlen_k=None,
+        index_attn_max_topk=0, max_seqlen_k=None, sparse_load_bwd=False,
     ):
         softmax_scale = (
             q.shape[-1] ** (-0.5) if softmax_scale is None else softmax_scale
         )
         assert q_ranges is not None and k_ranges is not None
         assert q_ranges.size(0) == k_ranges.size(0)
+        if sparse_load_bwd and not (sparse_load and auto_range_merge):
+            raise RuntimeError(
+                "sparse_load_bwd requires sparse_load=True (and with it "
+                "auto_range_merge=True)")
         fwd_q_ranges, fwd_k_ranges, fwd_tm = q_ranges, k_ranges, attn_type_map
         fwd_qk_starts = None
         if auto_range_merge:
@@ -663,6 +679,8 @@ class FlexFlashAttnFunc(torch.autograd.Function):
         # avoid a per-backward device sync to size the bwd grid
         ctx.max_seqlen_k = max_seqlen_k
         ctx.cat_gqa = cat_gqa
+        # a switch of its own: sparse_load alone keeps the usual dQ pass
+        ctx.sparse_load_bwd = bool(sparse_load_bwd)
         if max_logits is not None:
             ctx.mark_non_differentiable(max_logits)
         return out, lse, max_logits
@@ -689,7 +707,7 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             auto_range_merge=ctx.auto_range_merge,
             disable_bwd_dq_atomic_reduction=(
                 direct_ok and ctx.disable_bwd_dq_atomic_reduction),
-            cat_gqa=ctx.cat_gqa,
+            cat_gqa=ctx.cat_gqa, sparse_load=ctx.sparse_load_bwd,
         )
         if sink is not None and dsink is not None:
             dsink = dsink.to(sink.dtype)
@@ -729,6 +747,7 @@ def flex_flash_attn_func(
     swap_bwd_qk_loop: bool = False,
     return_max_logits: bool = False,
     max_seqlen_k: Optional[int] = None,
+    sparse_load_bwd: bool = False,
 ) -> tuple[torch.Tensor, AttnForwardMeta]:
     """Single-GPU flex-flash-attention (drop-in for the reference
     flex_flash_attn_func, flex_flash_attn.py:1066; full mask semantics in the
@@ -803,13 +822,33 @@ def flex_flash_attn_func(
     would be served as a full one. out, lse and max_logits agree with the
     default launch within rounding (not bit for bit); pack_gqa, softcap, sink,
     direct store, sm_margin and return_max_logits compose with it, and the
-    backward is the usual one. fp8 inputs and head dims above 128 accept the
+    backward is the usual one (but see sparse_load_bwd below). fp8 inputs and
+    head dims above 128 accept the
     flag and run the default launch, which for fp8 (past this function's
     refusal of fp8 + auto_range_merge, see above) is the fp8 kernel's segment
     loop over the merged table. Whether it pays is measured in
     profiles/fwd_sparse_load.md: with the direct store it does for k blocks
     below 64 rows, the crossover lying between 64 and 128; in merge mode only
     at 16 rows.
+
+    sparse_load_bwd=True (a switch of its own: sparse_load alone leaves the
+    backward as it is; it requires sparse_load=True, RuntimeError otherwise)
+    does the same to the dQ pass of the backward: the dQ kernel lays the k
+    ranges of a (unique) q range end to end and gathers 64 rows per K/V stage
+    across them, where the usual pass stages every k range on its own, with
+    whole stages, a pipeline restart and a drain each. The promise is the
+    forward's: every slice a full block, attn_type_map is not read by that
+    kernel. dq agrees with the usual pass within rounding, not bit for bit;
+    dk and dv are the usual pass's (the dK/dV kernels are untouched). bf16 /
+    fp16 and head dims up to 128; fp8 inputs reached through
+    FlexFlashAttnFunc.apply take it through their bf16-upcast backward; head
+    dims above 128 accept the flag and run the usual pass. The
+    context-parallel runtime does not pass it. Where it pays is measured in
+    profiles/bwd_sparse_load.md: at 16k tokens and 128-row q blocks the dQ
+    pass gains 8 % with 16-row k blocks, 3 % with 32-row ones and about 1 %,
+    the run-to-run spread, from 64 rows on (whole backward step: 6 %, 2 %,
+    nothing); it never lost. The pass stays bound by its grid over the
+    table's entries, which the flag does not change.
 
     Backward stores (range path, bf16 / fp16). By default dq, dk and dv are
     accumulated with atomics in f32 buffers and cast once at the end.
@@ -846,6 +885,8 @@ def flex_flash_attn_func(
     assert not (sparse_load and _has_index), (
         "sparse_load and index_attn_indices are mutually exclusive"
     )
+    if sparse_load_bwd and not sparse_load:
+        raise RuntimeError("sparse_load_bwd requires sparse_load=True.")
     if sparse_load and not auto_range_merge:
         raise RuntimeError("When using sparse load, range merge must be enabled.")
     # This function's own refusal is existing, tested behaviour and stays. The
@@ -954,6 +995,7 @@ def flex_flash_attn_func(
             auto_range_merge=auto_range_merge,
             return_max_logits=return_max_logits,
             pack_gqa=pack_gqa, cat_gqa=cat_gqa, sparse_load=sparse_load,
+            sparse_load_bwd=sparse_load_bwd,
         )
         return out[..., :d], meta
     out, lse, max_logits = FlexFlashAttnFunc.apply(
@@ -962,6 +1004,6 @@ def flex_flash_attn_func(
         disable_fwd_atomic_reduction, disable_bwd_dkv_atomic_reduction,
         ref_block_size, max_seqlen_q, auto_range_merge, swap_ab, pack_gqa,
         cat_gqa, sparse_load, index_attn, swap_bwd_qk_loop, return_max_logits,
-        None, 0, max_seqlen_k,
+        None, 0, max_seqlen_k, sparse_load_bwd,
     )
     return out, AttnForwardMeta(lse=lse, max_logits=max_logits)
