@@ -381,6 +381,38 @@ typedef struct magi_ffa_bwd_sparse_args {
 int magi_ffa_bwd_dq_sparse(const magi_ffa_bwd_sparse_args* args);
 int magi_ffa_bwd_sparse_args_size(void);
 
+/* swap_bwd_qk_loop (reference flex_flash_attn_func: "Q for outer-loop and K
+ * for inner-loop" in the backward): ONE q-outer pass in place of the dq pass
+ * and the dkv pass. A workgroup owns what a dq workgroup owns, (q range - the
+ * unique one under seg_starts -, q head, block of 128 q rows), walks the k
+ * segments of that unit once and produces all three gradients: S and dP are
+ * recomputed once per tile (5 matmuls where the two passes spend 3 + 4), dQ
+ * stays in registers and is stored once, and dK / dV go out with one f32
+ * atomic add per non-zero element and 32-row k tile, reduced over the 128 q
+ * rows of the workgroup first, into row k and KV head h / (hq / hk). Needs
+ * dpsum filled (magi_ffa_bwd_preprocess).
+ *   args.dq          zeroed f32, or with dq_is_16bit a zeroed elem_type buffer
+ *                    stored directly (disjoint q ranges), as in
+ *                    magi_ffa_bwd_dq_direct.
+ *   args.dk, dv      zeroed f32 accumulators: dkv_is_16bit must be 0. Several
+ *                    workgroups add into one row, whatever the ranges are.
+ *   args.seg_starts  optional: NULL = one k segment per q range (the flat
+ *                    table), else the dq pass's merged table.
+ *   attn_type_map    is read, all four types; softcap, both element types,
+ *                    GQA and cu_margin's low 16 bits (the strided grid) apply
+ *                    as in the dq pass. k rows and q rows in no range keep the
+ *                    caller's zeros. Results agree with the two passes within
+ *                    rounding, not bit for bit; f32 atomics reorder, so there
+ *                    is no deterministic mode.
+ * Built for d = 64 and 128; any other head dim is an error here (the caller
+ * falls back to the two passes). Validation, in this order, all before any
+ * HIP call: -1 null struct or null dout / q / k / v / lse / dq / dk / dv /
+ * dpsum, -2 head dim not 64 or 128, -3 hk <= 0 or hq % hk != 0, -9 elem_type,
+ * -12 a deterministic GQA head split packed into cu_margin's top 16 bits, -16
+ * dkv_is_16bit != 0; then n_ranges <= 0 returns 0 without a launch; -5 more
+ * than 65535 ranges. */
+int magi_ffa_bwd_qloop(const magi_ffa_bwd_direct_args* args);
+
 /* ------------------------------------------------------------------ *
  * Range row ops (reference common/range_op/_range_*.py — Triton there,
  * hand-written HIP here; pack/unpack engine of the group collectives). *

@@ -331,6 +331,8 @@ def _try_load() -> ctypes.CDLL | None:
             ("magi_ffa_bwd_cat_args_size", []),
             ("magi_ffa_bwd_dq_sparse", [ctypes.POINTER(MagiFfaBwdSparseArgs)]),
             ("magi_ffa_bwd_sparse_args_size", []),
+            # swap_bwd_qk_loop: dq, dk and dv in one q-outer pass
+            ("magi_ffa_bwd_qloop", [ctypes.POINTER(MagiFfaBwdDirectArgs)]),
             ("magi_range_gather", [ctypes.POINTER(MagiRangeOpArgs)]),
             ("magi_range_reduce", [ctypes.POINTER(MagiRangeOpArgs)]),
             ("magi_correct_out_lse", [ctypes.POINTER(MagiCorrectArgs)]),

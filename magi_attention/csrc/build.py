@@ -24,6 +24,7 @@ SOURCES = [
     CSRC / "ffa_index_bwd.hip",
     CSRC / "ffa_index_fp8.hip",
     CSRC / "ffa_bwd.hip",
+    CSRC / "ffa_bwd_qloop.hip",
     CSRC / "range_ops.hip",
     CSRC / "ffa_fwd_fp8.hip",
     CSRC / "ext_utils.hip",
@@ -34,6 +35,7 @@ SOURCES = [
 HEADERS = [
     CSRC / "ffa_device.h",
     CSRC / "ffa_bwd_dq_body.h",
+    CSRC / "ffa_bwd_common.h",
     PKG.parent / "include" / "magi_ffa.h",
 ]
 

@@ -383,13 +383,46 @@ def run_bwd_passes(args, device, dq_tables=None, dkv_tables=None,
     del k_cum  # main is ordered behind the dq kernel from here on
 
 
+def bwd_swap_active(swap_bwd_qk_loop, dtype: torch.dtype, d: int) -> bool:
+    """Whether a backward with this flag runs the one-pass q-outer kernel:
+    there is one built for it (16-bit, d = 64 or 128). Otherwise the flag is
+    accepted and the two passes run."""
+    return (bool(swap_bwd_qk_loop)
+            and dtype in (torch.bfloat16, torch.float16) and d in (64, 128))
+
+
+def run_bwd_qloop(args, dq_tables=None) -> None:
+    """swap_bwd_qk_loop (the caller has applied bwd_swap_active): dq, dk and
+    dv from magi_ffa_bwd_qloop alone, on the current stream - no side stream,
+    no dK/dV launch. dq_tables: the dq pass's merged table of run_bwd_passes
+    under auto_range_merge (the caller keeps it alive), else args' flat one.
+    dk and dv are f32 accumulators."""
+    if dq_tables is not None:
+        outer, inner, tm, starts = dq_tables
+        args.q_ranges, args.k_ranges = ptr(outer), ptr(inner)
+        args.attn_type_map, args.seg_starts = ptr(tm), ptr(starts)
+    else:
+        args.seg_starts = None
+    args.stream = current_stream_ptr()
+    check(_ffa_lib.lib().magi_ffa_bwd_qloop(args), "magi_ffa_bwd_qloop")
+
+
 def run_bwd(args, q_ranges, k_ranges, attn_type_map, device, *,
-            deterministic: bool, merged=None, sparse_load=False) -> None:
+            deterministic: bool, merged=None, sparse_load=False,
+            swap_qk_loop=False) -> None:
     """The dq/dk/dv passes over a filled, preprocessed args; merged =
     (dq_tables, dkv_tables) of run_bwd_passes under auto_range_merge, and
     sparse_load its switch (merged tables only, which deterministic mode
-    refuses, so it never meets the flag)."""
-    if deterministic:
+    refuses, so it never meets the flag). swap_qk_loop (where bwd_swap_active):
+    the one-pass kernel in place of them all, over merged[0] if there is one;
+    sparse_load configures a pass that then does not run."""
+    if swap_qk_loop:
+        assert not deterministic, (
+            "Deterministic mode is not supported when swap_bwd_qk_loop is "
+            "enabled."
+        )
+        run_bwd_qloop(args, merged[0] if merged else None)
+    elif deterministic:
         assert merged is None, "no deterministic mode over merged tables"
         run_bwd_deterministic(args, q_ranges, k_ranges, attn_type_map)
     else:

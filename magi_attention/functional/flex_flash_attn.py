@@ -476,10 +476,26 @@ def _flex_flash_attn_backward(
     disable_bwd_dq_atomic_reduction: bool = False,
     cat_gqa: bool = False,
     sparse_load: bool = False,
+    swap_bwd_qk_loop: bool = False,
     **_unused,
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """Dense (range-table) backward; returns (dq, dk, dv, dsink). q/k/v are
     all bf16 or all fp16 (the autograd function upcasts fp8 before it calls).
+
+    swap_bwd_qk_loop (reference flex_flash_attn.py:1216) takes effect where
+    _ffa_launch.bwd_swap_active says so (bf16 / fp16, head dim 64 or 128;
+    otherwise the flag is accepted and the two passes run): after the
+    preprocess ONE q-outer kernel (csrc/ffa_bwd_qloop.hip) produces dq, dk
+    and dv on the current stream, in place of the dQ pass and the dK/dV pass.
+    A workgroup owns 128 q rows of a (unique) q range and a q head, walks the
+    range's k segments once, keeps dQ in registers and adds dK/dV with f32
+    atomics per 32-row k tile, reduced over its q rows first. dk and dv are
+    therefore always f32 accumulators: the flag refuses
+    disable_bwd_dkv_atomic_reduction (RuntimeError, as in the reference) and
+    deterministic. disable_bwd_dq_atomic_reduction still stores dq directly.
+    Under auto_range_merge only the q-merged table is built (reference
+    :962-971). cat_gqa and sparse_load configure passes that do not run and
+    have no effect. The gradients agree with the two passes within rounding.
 
     By default dq, dk and dv are zeroed f32 buffers that the kernels add
     their register tiles into with atomics, because ranges may overlap and
@@ -542,6 +558,15 @@ def _flex_flash_attn_backward(
     assert out.dtype in (torch.float32, q.dtype)
     dout = dout.to(q.dtype)
 
+    if swap_bwd_qk_loop and disable_bwd_dkv_atomic_reduction:
+        raise RuntimeError(
+            "When disable_bwd_dkv_atomic_reduction is true, swap_bwd_qk_loop "
+            "must be false."
+        )
+    assert not (swap_bwd_qk_loop and deterministic), (
+        "Deterministic mode is not supported when swap_bwd_qk_loop is enabled."
+    )
+    swap = _ffa_launch.bwd_swap_active(swap_bwd_qk_loop, q.dtype, q.shape[-1])
     direct_dq = bool(disable_bwd_dq_atomic_reduction)
     cat_gqa = bool(cat_gqa) and hq != hk
     direct_dkv = bool(disable_bwd_dkv_atomic_reduction) and (
@@ -600,13 +625,16 @@ def _flex_flash_attn_backward(
     elif auto_range_merge:
         # dq pass: unique q ranges with k segments; dkv pass: unique k
         # ranges with q segments (reference bwd_kq_map)
+        # (the one-pass kernel is q-outer: no k-merged table for it)
         merged = (_merged_tables(q_ranges, k_ranges, attn_type_map),
+                  None if swap else
                   _merged_tables(k_ranges, q_ranges, attn_type_map))
     _ffa_launch.run_bwd(
         args, q_ranges, k_ranges, attn_type_map, q.device,
         deterministic=deterministic, merged=merged,
         sparse_load=_ffa_launch.bwd_sparse_load_active(
             sparse_load, q.dtype, q.shape[-1], merged and merged[0]),
+        swap_qk_loop=swap,
     )
     return dq, dk, dv, dsink
 
@@ -635,6 +663,11 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             raise RuntimeError(
                 "sparse_load_bwd requires sparse_load=True (and with it "
                 "auto_range_merge=True)")
+        if disable_bwd_dkv_atomic_reduction and swap_bwd_qk_loop:
+            raise RuntimeError(
+                "When disable_bwd_dkv_atomic_reduction is true, "
+                "swap_bwd_qk_loop must be false."
+            )
         fwd_q_ranges, fwd_k_ranges, fwd_tm = q_ranges, k_ranges, attn_type_map
         fwd_qk_starts = None
         if auto_range_merge:
@@ -681,6 +714,7 @@ class FlexFlashAttnFunc(torch.autograd.Function):
         ctx.cat_gqa = cat_gqa
         # a switch of its own: sparse_load alone keeps the usual dQ pass
         ctx.sparse_load_bwd = bool(sparse_load_bwd)
+        ctx.swap_bwd_qk_loop = bool(swap_bwd_qk_loop)
         if max_logits is not None:
             ctx.mark_non_differentiable(max_logits)
         return out, lse, max_logits
@@ -708,6 +742,7 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             disable_bwd_dq_atomic_reduction=(
                 direct_ok and ctx.disable_bwd_dq_atomic_reduction),
             cat_gqa=ctx.cat_gqa, sparse_load=ctx.sparse_load_bwd,
+            swap_bwd_qk_loop=ctx.swap_bwd_qk_loop,
         )
         if sink is not None and dsink is not None:
             dsink = dsink.to(sink.dtype)
@@ -850,6 +885,29 @@ def flex_flash_attn_func(
     nothing); it never lost. The pass stays bound by its grid over the
     table's entries, which the flag does not change.
 
+    swap_bwd_qk_loop=True (range path, bf16 / fp16, head dims up to 128;
+    reference: "Q for outer-loop and K for inner-loop" in the backward): after
+    the preprocess ONE q-outer kernel produces dq, dk and dv, in place of the
+    dQ pass and the dK/dV pass. A workgroup owns 128 q rows of a q range (with
+    auto_range_merge: of a unique q range, and only the q-merged table is
+    built) and a q head, walks the range's k ranges once, recomputes S and dP
+    once per tile, keeps dQ in registers and adds dK/dV with f32 atomics per
+    32-row k tile, reduced over its q rows first. dk and dv are therefore f32
+    accumulators cast once at return: the flag cannot be combined with
+    disable_bwd_dkv_atomic_reduction (RuntimeError) or deterministic
+    (AssertionError), as in the reference; disable_fwd_atomic_reduction still
+    stores dq directly. All four mask types, softcap, sink, GQA, sm_margin and
+    padded head dims compose with it; fp8 inputs take it through their
+    bf16-upcast backward; cat_gqa and sparse_load_bwd are accepted and have no
+    effect (they configure passes that do not run), as pack_gqa has none in
+    any backward. Head dims above 128 accept the flag and run the two passes;
+    index_attn_indices ignores it and the context-parallel runtime does not
+    pass it. The gradients agree with the two passes within rounding.
+    Measured (profiles/bwd_swap_qk_loop.md), it does not pay: at 16k tokens
+    the backward step takes 2.1 to 2.5 times as long on block-sparse tables
+    with k blocks of 16 to 128 rows, 2.6 times on a dense causal mask and 2.0
+    times on 8 x 2k documents. Leave it off unless you measure otherwise.
+
     Backward stores (range path, bf16 / fp16). By default dq, dk and dv are
     accumulated with atomics in f32 buffers and cast once at the end.
     disable_bwd_dkv_atomic_reduction=True is the promise that the k ranges
@@ -875,6 +933,9 @@ def flex_flash_attn_func(
     partial gradients are reduced across ranks in f32. What the direct
     stores save is measured in profiles/bwd_direct_store.md."""
     assert not (pack_gqa and cat_gqa), "pack_gqa and cat_gqa cannot be both True"
+    assert not (swap_bwd_qk_loop and deterministic), (
+        "Deterministic mode is not supported when swap_bwd_qk_loop is enabled."
+    )
     # ── sparse-input validation (mirrors reference :1344-1384) ──
     _has_ranges = q_ranges is not None
     _has_index = index_attn_indices is not None
@@ -996,6 +1057,7 @@ def flex_flash_attn_func(
             return_max_logits=return_max_logits,
             pack_gqa=pack_gqa, cat_gqa=cat_gqa, sparse_load=sparse_load,
             sparse_load_bwd=sparse_load_bwd,
+            swap_bwd_qk_loop=swap_bwd_qk_loop,
         )
         return out[..., :d], meta
     out, lse, max_logits = FlexFlashAttnFunc.apply(
