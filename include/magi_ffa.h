@@ -614,6 +614,59 @@ typedef struct magi_ffa_index_bwd_args {
 
 int magi_ffa_bwd_index(const magi_ffa_index_bwd_args* args);
 
+/* q_block_size on the index path (the reference declares it on
+ * flex_flash_attn_func): one index row per block of q_block_size q token
+ * rows. Rows [b*B, min((b+1)*B, total_q)) of q, with all their hq heads,
+ * attend the K rows listed in indices_2d[b], so indices_2d is
+ * [ceil(total_q / B), max_topk] for these entries (the last block may be
+ * partial); -1 tail padding, 64 | max_topk, hk == 1 and global row ids are as
+ * above. With KV heads folded into q rows, arranging rows so that a block
+ * belongs to one KV head is the caller's business. The switch rides behind an
+ * embedded copy of the base struct, as pack_gqa rides behind
+ * magi_ffa_fwd_args; the base entries and their kernels are untouched.
+ *
+ * The kernels are BLOCK instantiations of ffa_index.hip / ffa_index_bwd.hip:
+ * q is [total_q, hq, d], so a block's B*hq (token, head) rows are one
+ * contiguous slab of flat rows and take the place of the hq heads of a token -
+ * a workgroup is (block, chunk of 32*W packed rows), W from B*hq as the base
+ * entries take it from hq (4 waves above 64 rows, 2 above 32, else 1). The
+ * MFMA tiles fill with B*hq rows, K/V are gathered once per workgroup and not
+ * once per token, and the backward issues one dK/dV atomic per (workgroup,
+ * gathered row) for all the tokens of the chunk. A block whose list is all -1
+ * leaves out at 0 and writes lse = lse_sink for its live rows with a sink,
+ * else leaves -inf. sink (sink_ssh 0 and 1, by the row's own token and head),
+ * max_logits ([hq], by the row's head), softcap and out_is_fp32 act as in the
+ * base entries; magi_ffa_bwd_preprocess and magi_ffa_dsink are row-wise and
+ * serve both. Results agree with the base entry over lists expanded to one per
+ * token within rounding, not bit for bit: packing changes which rows share a
+ * wave, and the deferred-max decision is per wave. q_block_size = 1 computes
+ * what the base entry computes, through the BLOCK kernels; a q_block_size
+ * beyond total_q is one block.
+ *   reserved  not read.
+ * Validation is the base entry's, same order and codes, all before any HIP
+ * call, then the next code for q_block_size < 1: -6 for
+ * magi_ffa_fwd_index_block (after -1 .. -5), -5 for magi_ffa_bwd_index_block
+ * (after -1 .. -4); then total_q <= 0 returns 0 without a launch. A null
+ * struct is -1. There is no fp8 block entry. The *_args_size functions return
+ * sizeof of the structs as compiled (magi_ffa_args_size keeps its list). */
+typedef struct magi_ffa_index_block_args {
+  magi_ffa_index_args args;   /* indices_2d: [ceil(total_q / B), max_topk] */
+  int32_t q_block_size;       /* B >= 1 */
+  int32_t reserved;
+} magi_ffa_index_block_args;
+
+int magi_ffa_fwd_index_block(const magi_ffa_index_block_args* args);
+int magi_ffa_fwd_index_block_args_size(void);
+
+typedef struct magi_ffa_index_bwd_block_args {
+  magi_ffa_index_bwd_args args;
+  int32_t q_block_size;       /* B >= 1 */
+  int32_t reserved;
+} magi_ffa_index_bwd_block_args;
+
+int magi_ffa_bwd_index_block(const magi_ffa_index_bwd_block_args* args);
+int magi_ffa_bwd_index_block_args_size(void);
+
 /* Version/identity probe so tests can verify the native library is loaded. */
 int magi_ffa_abi_version(void);
 

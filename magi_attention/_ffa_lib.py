@@ -283,6 +283,29 @@ class MagiFfaIndexBwdArgs(ctypes.Structure):
     ]
 
 
+# one index row per q_block_size q token rows: indices_2d is
+# [ceil(total_q / q_block_size), max_topk] for the two *_block entries
+_Q_BLOCK_FIELDS = [
+    ("q_block_size", ctypes.c_int32),  # >= 1
+    ("reserved", ctypes.c_int32),
+]
+
+
+class MagiFfaIndexBlockArgs(_MagiFfaIndexArgsFull):
+    """mirrors magi_ffa_index_block_args: magi_ffa_index_args embedded first
+    (see MagiFfaBwdDirectArgs), then the q_block_size of
+    magi_ffa_fwd_index_block"""
+
+    _fields_ = _Q_BLOCK_FIELDS
+
+
+class MagiFfaIndexBwdBlockArgs(MagiFfaIndexBwdArgs):
+    """mirrors magi_ffa_index_bwd_block_args: magi_ffa_index_bwd_args embedded
+    first, then the q_block_size of magi_ffa_bwd_index_block"""
+
+    _fields_ = _Q_BLOCK_FIELDS
+
+
 class MagiCorrectArgs(ctypes.Structure):
     _fields_ = [
         ("out1", ctypes.c_void_p),
@@ -314,6 +337,12 @@ def _try_load() -> ctypes.CDLL | None:
             ("magi_ffa_fwd_index", [ctypes.POINTER(MagiFfaIndexArgs)]),
             ("magi_ffa_fwd_index_fp8", [ctypes.POINTER(MagiFfaIndexArgs)]),
             ("magi_ffa_bwd_index", [ctypes.POINTER(MagiFfaIndexBwdArgs)]),
+            ("magi_ffa_fwd_index_block",
+             [ctypes.POINTER(MagiFfaIndexBlockArgs)]),
+            ("magi_ffa_fwd_index_block_args_size", []),
+            ("magi_ffa_bwd_index_block",
+             [ctypes.POINTER(MagiFfaIndexBwdBlockArgs)]),
+            ("magi_ffa_bwd_index_block_args_size", []),
             ("magi_ffa_bwd", [ctypes.POINTER(MagiFfaBwdArgs)]),
             ("magi_ffa_bwd_dq", [ctypes.POINTER(MagiFfaBwdArgs)]),
             ("magi_ffa_bwd_dkv", [ctypes.POINTER(MagiFfaBwdArgs)]),
@@ -371,6 +400,9 @@ def _try_load() -> ctypes.CDLL | None:
             (MagiFfaBwdDirectArgs, lib.magi_ffa_bwd_direct_args_size()),
             (MagiFfaBwdCatArgs, lib.magi_ffa_bwd_cat_args_size()),
             (MagiFfaBwdSparseArgs, lib.magi_ffa_bwd_sparse_args_size()),
+            (MagiFfaIndexBlockArgs, lib.magi_ffa_fwd_index_block_args_size()),
+            (MagiFfaIndexBwdBlockArgs,
+             lib.magi_ffa_bwd_index_block_args_size()),
         ]:
             if ctypes.sizeof(cls) != size:
                 raise RuntimeError(

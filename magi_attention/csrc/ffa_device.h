@@ -10,11 +10,13 @@
 //               (the bf16 kernels), to_fp8, cframe_to_afrag_fp8 (the fp8 ones)
 //   softmax     FP8_MAX_OFFSET, softmax_step_fp8 (ffa_fwd_fp8, ffa_index_fp8)
 //   index host  IdxFwdParams<T>, index_fwd_entry: the one host path of
-//               magi_ffa_fwd_index and magi_ffa_fwd_index_fp8
+//               magi_ffa_fwd_index, magi_ffa_fwd_index_fp8 and
+//               magi_ffa_fwd_index_block; index_waves (the backward too)
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "../../include/magi_ffa.h"
@@ -398,20 +400,34 @@ struct IdxFwdParams {
   int s_sink;
   int sink_ssh;
   float* max_logits;  // [hq], null = off
+  int q_block;        // BLOCK kernels only: q token rows per index row
 };
 
-// Body of magi_ffa_fwd_index / magi_ffa_fwd_index_fp8: checks, params, launch
-// shape and dispatch. launch(D, W, HAS_SOFTCAP, OUT_BF16, grid, block, stream,
-// p) gets the four template arguments as std::integral_constant values and
-// launches its kernel. Nothing before that call touches the HIP runtime.
+// Wave count of an index workgroup from the rows that share one index row
+// (hq, or q_block_size * hq): 32 rows per wave, so one wave-set covers them
+// up to 128 rows (DiT ratio 128 -> 4 waves; small-ratio MHA shapes keep lanes
+// busy at W=1). The forwards and the backward share the rule.
+static inline int index_waves(long long rows) {
+  return (rows > 64) ? 4 : (rows > 32 ? 2 : 1);
+}
+
+// Body of magi_ffa_fwd_index / magi_ffa_fwd_index_fp8 / _block: checks,
+// params, launch shape and dispatch. launch(D, W, HAS_SOFTCAP, OUT_BF16, grid,
+// block, stream, p) gets the four template arguments as
+// std::integral_constant values and launches its kernel. Nothing before that
+// call touches the HIP runtime. q_block (magi_ffa_fwd_index_block only): q
+// token rows per index row; the grid is then (row blocks, chunks of 32*W
+// packed rows) and launch starts the BLOCK kernels.
 template <class T, class Launch>
-static int index_fwd_entry(const magi_ffa_index_args* a, Launch launch) {
+static int index_fwd_entry(const magi_ffa_index_args* a, Launch launch,
+                           const int32_t* q_block = nullptr) {
   if (!a || !a->q || !a->k || !a->v || !a->out || !a->lse || !a->indices_2d)
     return -1;
   if (a->d != 64 && a->d != 128) return -2;
   if (a->hk != 1) return -3;  // kv heads are folded into K rows (magi_ffa.h)
   if (a->max_topk <= 0 || (a->max_topk & 63) != 0) return -4;
   if (a->sink && (a->s_sink < 1 || a->s_sink > 8)) return -5;
+  if (q_block && *q_block < 1) return -6;
   if (a->total_q <= 0 || a->hq <= 0) return 0;
 
   IdxFwdParams<T> p;
@@ -432,13 +448,16 @@ static int index_fwd_entry(const magi_ffa_index_args* a, Launch launch) {
   p.s_sink = a->s_sink;
   p.sink_ssh = a->sink_ssh;
   p.max_logits = a->max_logits;
+  // a block longer than q is the one block [0, total_q)
+  p.q_block = q_block ? (int)std::min<long long>(*q_block, a->total_q) : 1;
 
-  // head-block = 32*W query heads; pick W so one wave-set covers hq (DiT
-  // ratio 128 -> 4 waves; small-ratio MHA shapes keep lanes busy at W=1)
-  const int w = (a->hq > 64) ? 4 : (a->hq > 32 ? 2 : 1);
+  // head-block = 32*W rows of the hq (x q_block) that share an index row
+  const long long qb = p.q_block;
+  const long long rows = qb * a->hq;
+  const int w = index_waves(rows);
   const int span = 32 * w;
-  const dim3 grid((unsigned)a->total_q, (unsigned)((a->hq + span - 1) / span),
-                  1);
+  const dim3 grid((unsigned)((a->total_q + qb - 1) / qb),
+                  (unsigned)((rows + span - 1) / span), 1);
   const dim3 block(64 * w);
   const hipStream_t stream = (hipStream_t)a->stream;
   const bool sc = a->softcap > 0.f;

@@ -24,6 +24,15 @@
 // Compute core (swapped QK^T, softmax layout, defer-max, cvt_pk P rebuild,
 // tr16 V fragments) is the same design as ffa_fwd.hip — see the notes there.
 //
+// BLOCK instantiations (magi_ffa_fwd_index_block, q_block_size = B): one
+// index row per block of B q token rows. A block's B*hq (token, head) rows
+// are contiguous flat rows of q, so they take the place of the hq heads: one
+// workgroup owns (block, chunk of 32*W packed rows), the tiles fill with
+// B*hq rows and K/V are gathered once per workgroup, not once per token. The
+// defer-max decision is per wave, so results agree with the per-token kernel
+// over expanded lists within rounding, not bit for bit. The default
+// instantiations take the BLOCK = false arm everywhere and keep their code.
+//
 // Epilogue extras, both off (null pointers, block-uniform branches, k loop
 // untouched, out/lse bit-identical) unless asked for:
 //   - attention sink: a lane owns one query head, so it loads that head's
@@ -43,14 +52,27 @@
 
 #define IDX_BN 32  // k rows per inner MFMA tile
 
-template <int D, bool HAS_SOFTCAP, bool OUT_BF16, int WAVES>
+template <int D, bool HAS_SOFTCAP, bool OUT_BF16, int WAVES, bool BLOCK = false>
 __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     IdxFwdParams<bf16_t> p) {
   constexpr int DF = D / 16;
   constexpr int DT = D / 32;
 
+  // Row space of the workgroup's index row. Default: the hq heads of token
+  // blockIdx.x. BLOCK: the q_block tokens of block blockIdx.x with all their
+  // heads - q is [total_q, hq, d], so they are the contiguous slab of flat
+  // rows flat(r), r < nrows (the last block may be partial). Everything below
+  // indexes q / out / lse by flat(r) and bounds r by nrows; token and head of
+  // a row (r / hq, r % hq) matter to the sink and max_logits only. The
+  // default arm of each is the expression the per-token kernel always had.
   const long long tok = blockIdx.x;
   const int h0 = blockIdx.y * (32 * WAVES);
+  const long long tok0 = BLOCK ? tok * p.q_block : tok;  // first token
+  const int nrows =
+      BLOCK ? (int)min((long long)p.q_block, p.total_q - tok0) * p.hq : p.hq;
+  auto flat = [&](int r) { return tok0 * p.hq + r; };
+  auto row_tok = [&](int r) { return BLOCK ? tok0 + r / p.hq : tok; };
+  auto row_head = [&](int r) { return BLOCK ? r % p.hq : r; };
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -64,20 +86,22 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     // softmax mass is the sink's alone: lse = lse_sink, out stays 0
     if (p.sink) {
       const int eh = h0 + wave * 32 + lo32;
-      if (eh < p.hq && hi == 0) {
-        const float ls =
-            index_sink_lse(p.sink, p.s_sink, p.sink_ssh, tok, p.hq, eh);
-        if (ls != -INFINITY) p.lse[tok * p.hq + eh] = ls;
+      if (eh < nrows && hi == 0) {
+        const float ls = index_sink_lse(p.sink, p.s_sink, p.sink_ssh,
+                                        row_tok(eh), p.hq, row_head(eh));
+        if (ls != -INFINITY) p.lse[flat(eh)] = ls;
       }
     }
     return;
   }
+  // a partial last block may leave whole workgroups without a row
+  if (BLOCK && h0 >= nrows) return;
 
-  const int q0 = h0 + wave * 32;       // first query head of this wave
-  const int qh = q0 + lo32;            // this lane's query head
-  const bool qvalid = qh < p.hq;
-  const bool qvalid_any = q0 < p.hq;
-  const int qclamp = qvalid ? qh : (p.hq - 1);
+  const int q0 = h0 + wave * 32;       // first row (query head) of this wave
+  const int qh = q0 + lo32;            // this lane's row (BLOCK: packed row)
+  const bool qvalid = qh < nrows;
+  const bool qvalid_any = q0 < nrows;
+  const int qclamp = qvalid ? qh : (nrows - 1);
 
   const float sl2 = HAS_SOFTCAP ? p.softcap * 1.4426950408889634f
                                 : p.scale * 1.4426950408889634f;
@@ -111,7 +135,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
   // Q fragments in registers
   bf16x8 qf[DF];
   {
-    const bf16_t* qp = p.q + (tok * p.hq + qclamp) * (long long)D;
+    const bf16_t* qp = p.q + flat(qclamp) * (long long)D;
 #pragma unroll
     for (int dd = 0; dd < DF; ++dd)
       qf[dd] = *(const bf16x8*)(qp + dd * 16 + hi * 8);
@@ -164,7 +188,7 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     }
 
     // ---- mask (position >= count) + scale into exp2 domain ----
-    const bool interior = (q0 + 31 < p.hq) && (ns + IDX_BN <= count);
+    const bool interior = (q0 + 31 < nrows) && (ns + IDX_BN <= count);
     float t[16];
     float mx = -INFINITY;
     if (interior) {
@@ -279,24 +303,26 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
   // so it is the true max). Invalid heads are -inf and drop out; the sink
   // below does not enter.
   if (p.max_logits && qvalid && hi == 0)
-    head_atomic_max(p.max_logits + qh, m_run * 0.6931471805599453f);
+    head_atomic_max(p.max_logits + row_head(qh),
+                    m_run * 0.6931471805599453f);
   // sink fold, fp32, ahead of the single rounding of out: the output scale
   // rides on inv_l. Block-uniform branch; a null sink leaves both untouched.
   if (p.sink && qvalid)
     index_sink_fold(
-        index_sink_lse(p.sink, p.s_sink, p.sink_ssh, tok, p.hq, qh),
+        index_sink_lse(p.sink, p.s_sink, p.sink_ssh, row_tok(qh), p.hq,
+                       row_head(qh)),
         lse_new, inv_l);
 
   if (lse_new != -INFINITY && qvalid && hi == 0)
-    p.lse[tok * p.hq + qh] = lse_new;
+    p.lse[flat(qh)] = lse_new;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int src = crow(r, hi);
     const float ilq = __uint_as_float(
         __builtin_amdgcn_ds_bpermute(src << 2, __float_as_uint(inv_l)));
     const int qr = q0 + src;
-    if (qr >= p.hq || ilq <= 0.f) continue;
-    const long long base = (tok * p.hq + qr) * (long long)D;
+    if (qr >= nrows || ilq <= 0.f) continue;
+    const long long base = flat(qr) * (long long)D;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       const float val = acc_o[dt][r] * ilq;
@@ -316,4 +342,21 @@ extern "C" int magi_ffa_fwd_index(const magi_ffa_index_args* a) {
         hipLaunchKernelGGL((ffa_index_fwd_kernel<D(), SC(), OB(), W()>), grid,
                            block, 0, stream, p);
       });
+}
+
+// q_block_size entry: the BLOCK instantiations, one index row per q-row block
+extern "C" int magi_ffa_fwd_index_block(const magi_ffa_index_block_args* a) {
+  if (!a) return -1;
+  return index_fwd_entry<bf16_t>(
+      &a->args,
+      [](auto D, auto W, auto SC, auto OB, dim3 grid, dim3 block,
+         hipStream_t stream, const IdxFwdParams<bf16_t>& p) {
+        hipLaunchKernelGGL((ffa_index_fwd_kernel<D(), SC(), OB(), W(), true>),
+                           grid, block, 0, stream, p);
+      },
+      &a->q_block_size);
+}
+
+extern "C" int magi_ffa_fwd_index_block_args_size(void) {
+  return (int)sizeof(magi_ffa_index_block_args);
 }

@@ -31,6 +31,13 @@
 //     MFMA k loop and atomic traffic does not scale with W. Padding slots and
 //     out-of-range ids issue no atomic at all.
 // fp32 atomics reorder, so there is no deterministic mode.
+//
+// BLOCK instantiations (magi_ffa_bwd_index_block, q_block_size = B): "head"
+// above reads "packed row" - the B*hq (token, head) rows of a block of B q
+// token rows that share one index row, contiguous in q. Phase 1 is unchanged
+// per row; phase 2 reduces over rows of several tokens, so one atomic per
+// (workgroup, gathered row) replaces one per token. The LDS images are per
+// row and keep their sizes (the static_assert below covers every build).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -56,17 +63,28 @@ struct IdxBwdParams {
   float scale;
   float softcap;
   long long total_q, total_k;
+  int q_block;  // BLOCK kernels only: q token rows per index row
 };
 
-template <int D, bool HAS_SOFTCAP, int WAVES>
+template <int D, bool HAS_SOFTCAP, int WAVES, bool BLOCK = false>
 __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
     IdxBwdParams p) {
   constexpr int DF = D / 16;
   constexpr int DT = D / 32;
-  constexpr int HB = 32 * WAVES;  // query heads per workgroup
+  constexpr int HB = 32 * WAVES;  // rows (query heads) per workgroup
 
+  // Row space of the workgroup's index row, as in ffa_index.hip: the hq heads
+  // of token blockIdx.x, or under BLOCK the contiguous slab of flat rows
+  // flat(r), r < nrows, of the q_block tokens of block blockIdx.x. q, dout,
+  // lse, dpsum and dq are all indexed by the flat row, so nothing below needs
+  // a row's token or head; the phase-2 reduction over the workgroup's HB rows
+  // then spans tokens and one atomic serves them all.
   const long long tok = blockIdx.x;
   const int h0 = blockIdx.y * HB;
+  const long long tok0 = BLOCK ? tok * p.q_block : tok;  // first token
+  const int nrows =
+      BLOCK ? (int)min((long long)p.q_block, p.total_q - tok0) * p.hq : p.hq;
+  auto flat = [&](int r) { return tok0 * p.hq + r; };
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -76,11 +94,13 @@ __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
   const int* irow = p.idx2d + tok * (long long)p.max_topk;
   const int count = index_valid_count(irow, p.max_topk);
   if (count == 0) return;  // dq zero-init by the host; no dk/dv contribution
+  // a partial last block may leave whole workgroups without a row
+  if (BLOCK && h0 >= nrows) return;
 
-  const int q0 = h0 + wave * 32;  // first query head of this wave
-  const int qh = q0 + lo32;       // this lane's query head
-  const bool qvalid = qh < p.hq;
-  const int qclamp = qvalid ? qh : (p.hq - 1);
+  const int q0 = h0 + wave * 32;  // first row (query head) of this wave
+  const int qh = q0 + lo32;       // this lane's row (BLOCK: packed row)
+  const bool qvalid = qh < nrows;
+  const int qclamp = qvalid ? qh : (nrows - 1);
 
   const float log2e = 1.4426950408889634f;
   const float sl2 = HAS_SOFTCAP ? p.softcap * log2e : p.scale * log2e;
@@ -128,9 +148,9 @@ __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
     for (int gi = 0; gi < 32 / ROWS_PER_GLDS; ++gi) {
       const int r0 = 32 * wave + ROWS_PER_GLDS * gi;
       const int r = r0 + g_r;
-      const int hh = min(h0 + r, p.hq - 1);
+      const int hh = min(h0 + r, nrows - 1);
       const int cs = g_c ^ ((r & SW32M) << 1);
-      const long long src = (tok * p.hq + hh) * (long long)D + cs * 8;
+      const long long src = flat(hh) * (long long)D + cs * 8;
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) unsigned int*)(p.q + src),
           (__attribute__((address_space(3))) unsigned int*)(ismem + OFF_Q +
@@ -147,15 +167,15 @@ __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
   // ---- persistent per-wave operands: Q / dO B-fragments, lse, dpsum ----
   bf16x8 qf[DF], dof[DF];
   {
-    const long long base = (tok * p.hq + qclamp) * (long long)D;
+    const long long base = flat(qclamp) * (long long)D;
 #pragma unroll
     for (int dd = 0; dd < DF; ++dd) {
       qf[dd] = *(const bf16x8*)(p.q + base + dd * 16 + hi * 8);
       dof[dd] = *(const bf16x8*)(p.dout + base + dd * 16 + hi * 8);
     }
   }
-  const float lse_q = p.lse[tok * p.hq + qclamp];
-  const float dpsum_q = p.dpsum[tok * p.hq + qclamp];
+  const float lse_q = p.lse[flat(qclamp)];
+  const float dpsum_q = p.dpsum[flat(qclamp)];
   const bool row_live = qvalid && lse_q != INFINITY && lse_q != -INFINITY;
   const float lsc = row_live ? lse_q * log2e : 0.f;
 
@@ -334,8 +354,8 @@ __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int qr = q0 + crow(r, hi);
-    if (qr >= p.hq) continue;
-    const long long base = (tok * p.hq + qr) * (long long)D;
+    if (qr >= nrows) continue;
+    const long long base = flat(qr) * (long long)D;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
       p.dq[base + dt * 32 + lo32] = (bf16_t)acc_dq[dt][r];
@@ -345,26 +365,32 @@ __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
 // ------------------------------------------------------------------
 // launcher
 // ------------------------------------------------------------------
-template <int D, int W>
+template <int D, int W, bool BLOCK>
 static int launch_index_bwd(const IdxBwdParams& p, dim3 grid,
                             hipStream_t stream) {
   dim3 block(64 * W);
   if (p.softcap > 0.f)
-    hipLaunchKernelGGL((ffa_index_bwd_kernel<D, true, W>), grid, block, 0,
-                       stream, p);
+    hipLaunchKernelGGL((ffa_index_bwd_kernel<D, true, W, BLOCK>), grid, block,
+                       0, stream, p);
   else
-    hipLaunchKernelGGL((ffa_index_bwd_kernel<D, false, W>), grid, block, 0,
-                       stream, p);
+    hipLaunchKernelGGL((ffa_index_bwd_kernel<D, false, W, BLOCK>), grid, block,
+                       0, stream, p);
   return (int)hipGetLastError();
 }
 
-extern "C" int magi_ffa_bwd_index(const magi_ffa_index_bwd_args* a) {
+// Body of magi_ffa_bwd_index (q_block null: the default kernels, one index
+// row per token) and magi_ffa_bwd_index_block (the BLOCK kernels, one index
+// row per *q_block token rows).
+template <bool BLOCK>
+static int index_bwd_entry(const magi_ffa_index_bwd_args* a,
+                           const int32_t* q_block) {
   if (!a || !a->dout || !a->q || !a->k || !a->v || !a->lse || !a->dpsum ||
       !a->indices_2d || !a->dq || !a->dk || !a->dv)
     return -1;
   if (a->d != 64 && a->d != 128) return -2;
   if (a->hk != 1) return -3;  // kv heads are folded into K rows (see header)
   if (a->max_topk <= 0 || (a->max_topk & 63) != 0) return -4;
+  if (q_block && *q_block < 1) return -5;
   if (a->total_q <= 0 || a->total_k <= 0 || a->hq <= 0) return 0;
 
   IdxBwdParams p;
@@ -384,19 +410,39 @@ extern "C" int magi_ffa_bwd_index(const magi_ffa_index_bwd_args* a) {
   p.softcap = a->softcap;
   p.total_q = a->total_q;
   p.total_k = a->total_k;
+  // a block longer than q is the one block [0, total_q)
+  p.q_block = q_block ? (int)std::min<long long>(*q_block, a->total_q) : 1;
 
-  // head-block = 32*W query heads, the rule of index_fwd_entry (ffa_device.h)
-  const int w = (a->hq > 64) ? 4 : (a->hq > 32 ? 2 : 1);
+  // head-block = 32*W rows of the hq (x q_block) that share an index row, the
+  // rule of index_fwd_entry (ffa_device.h)
+  const long long qb = p.q_block;
+  const long long rows = qb * a->hq;
+  const int w = index_waves(rows);
   const int span = 32 * w;
-  const unsigned hblocks = (unsigned)((a->hq + span - 1) / span);
-  dim3 grid((unsigned)a->total_q, hblocks, 1);
+  dim3 grid((unsigned)((a->total_q + qb - 1) / qb),
+            (unsigned)((rows + span - 1) / span), 1);
   hipStream_t stream = (hipStream_t)a->stream;
   if (a->d == 64) {
-    if (w == 4) return launch_index_bwd<64, 4>(p, grid, stream);
-    if (w == 2) return launch_index_bwd<64, 2>(p, grid, stream);
-    return launch_index_bwd<64, 1>(p, grid, stream);
+    if (w == 4) return launch_index_bwd<64, 4, BLOCK>(p, grid, stream);
+    if (w == 2) return launch_index_bwd<64, 2, BLOCK>(p, grid, stream);
+    return launch_index_bwd<64, 1, BLOCK>(p, grid, stream);
   }
-  if (w == 4) return launch_index_bwd<128, 4>(p, grid, stream);
-  if (w == 2) return launch_index_bwd<128, 2>(p, grid, stream);
-  return launch_index_bwd<128, 1>(p, grid, stream);
+  if (w == 4) return launch_index_bwd<128, 4, BLOCK>(p, grid, stream);
+  if (w == 2) return launch_index_bwd<128, 2, BLOCK>(p, grid, stream);
+  return launch_index_bwd<128, 1, BLOCK>(p, grid, stream);
 }
+
+extern "C" int magi_ffa_bwd_index(const magi_ffa_index_bwd_args* a) {
+  return index_bwd_entry<false>(a, nullptr);
+}
+
+extern "C" int magi_ffa_bwd_index_block(
+    const magi_ffa_index_bwd_block_args* a) {
+  if (!a) return -1;
+  return index_bwd_entry<true>(&a->args, &a->q_block_size);
+}
+
+extern "C" int magi_ffa_bwd_index_block_args_size(void) {
+  return (int)sizeof(magi_ffa_index_bwd_block_args);
+}
+

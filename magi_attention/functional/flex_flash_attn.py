@@ -223,6 +223,7 @@ def _flex_flash_attn_forward_index(
     sink: Optional[torch.Tensor] = None,
     sink_layout: str = "sh",
     max_logits: Optional[torch.Tensor] = None,
+    q_block_size: int = 1,
 ) -> tuple[torch.Tensor, AttnForwardMeta]:
     """Index-attention (token-gather) forward: the reference's
     index_attn_indices direct-to-kernel path (flex_flash_attn.py:1358-1390).
@@ -230,6 +231,10 @@ def _flex_flash_attn_forward_index(
     row attends, shared by all hq query heads; -1 = contiguous tail padding.
     This is the forward pass; _flex_flash_attn_backward_index differentiates
     it (the reference backward receives None for index_attn).
+
+    q_block_size = B > 1 (bf16 only): indices_2d is [ceil(total_q / B),
+    max_topk] and row b serves q token rows [b*B, min((b+1)*B, total_q)); the
+    BLOCK kernels pack a block's B*hq (token, head) rows into their tiles.
 
     q/k/v are all bf16 (csrc/ffa_index.hip) or all fp8-e4m3
     (csrc/ffa_index_fp8.hip: raw e4m3 bytes, no descale factors, the fp8
@@ -255,8 +260,17 @@ def _flex_flash_attn_forward_index(
         "(k of shape [total_k, 1, d]; global id = (b*S_kv + t)*NHK + h)"
     )
     assert indices_2d.dtype == torch.int32 and indices_2d.dim() == 2
-    assert indices_2d.shape[0] == tq, (
-        f"indices_2d rows ({indices_2d.shape[0]}) must match q token rows ({tq})"
+    assert q_block_size >= 1, f"q_block_size must be >= 1, got {q_block_size}"
+    assert not (is_fp8 and q_block_size != 1), (
+        "index_attn with q_block_size > 1 is bf16 only: there is no fp8 "
+        "kernel for it"
+    )
+    n_blocks = -(-tq // q_block_size)
+    assert indices_2d.shape[0] == n_blocks, (
+        f"indices_2d rows ({indices_2d.shape[0]}) must match q token rows "
+        f"({tq})" if q_block_size == 1 else
+        f"indices_2d rows ({indices_2d.shape[0]}) must be ceil(total_q / "
+        f"q_block_size) = ceil({tq} / {q_block_size}) = {n_blocks}"
     )
     sink_f, s_sink = None, 0
     if sink is not None:
@@ -273,7 +287,7 @@ def _flex_flash_attn_forward_index(
     _ffa_launch.fwd_index(
         q, k, v, out, lse, indices_2d, softmax_scale, softcap,
         sink_f=sink_f, s_sink=s_sink, sink_ssh=sink_layout == "ssh",
-        max_logits=max_logits,
+        max_logits=max_logits, q_block_size=q_block_size,
     )
     return out, AttnForwardMeta(lse=lse, max_logits=max_logits)
 
@@ -310,11 +324,14 @@ def _flex_flash_attn_backward_index(
     softcap: float,
     sink: Optional[torch.Tensor] = None,
     sink_layout: str = "sh",
+    q_block_size: int = 1,
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """Index-attention backward (csrc/ffa_index_bwd.hip): dpsum preprocess,
     then one gather/scatter kernel. Returns (dq bf16, dk fp32, dv fp32, dsink):
     dq has a single owner per row and is stored directly; dk/dv are fp32
     accumulators the kernel scatters into with atomic adds (not deterministic).
+    q_block_size as in the forward: one atomic then serves all the tokens of
+    a workgroup's chunk of the block.
 
     With a sink, lse is the sink-corrected lse the forward saved and out the
     sink-scaled out, so the kernel's recomputed P and dpsum = rowsum(dO * O)
@@ -332,13 +349,15 @@ def _flex_flash_attn_backward_index(
     dsink = _ffa_launch.bwd_index(
         dout, q, k, v, out, lse, indices_2d, dq, dk, dv,
         softmax_scale, softcap, sink=sink, sink_layout=sink_layout,
+        q_block_size=q_block_size,
     )
     return dq, dk, dv, dsink
 
 
 def _index_attn_forward(ctx, q, k, v, indices_2d, softmax_scale, softcap,
-                        sink, sink_layout, return_max_logits):
-    """forward shared by IndexAttnFunc and IndexAttnSinkFunc"""
+                        sink, sink_layout, return_max_logits, q_block_size=1):
+    """forward shared by IndexAttnFunc, IndexAttnSinkFunc and
+    IndexAttnBlockFunc"""
     d = q.shape[-1]
     pad = _index_head_dim_pad(d) if q.dtype == torch.float8_e4m3fn else 0
     max_logits = (_ffa_launch.new_max_logits(q.shape[1], q.device)
@@ -347,8 +366,10 @@ def _index_attn_forward(ctx, q, k, v, indices_2d, softmax_scale, softcap,
         _pad_head_dim(q, pad), _pad_head_dim(k, pad), _pad_head_dim(v, pad),
         indices_2d, softmax_scale, softcap,
         sink=sink, sink_layout=sink_layout, max_logits=max_logits,
+        q_block_size=q_block_size,
     )
     ctx.save_for_backward(q, k, v, out, meta.lse, indices_2d, sink)
+    ctx.q_block_size = q_block_size
     ctx.softmax_scale = softmax_scale
     ctx.softcap = softcap
     ctx.pad = pad
@@ -376,6 +397,7 @@ def _index_attn_backward(ctx, dout, need_sink):
         dout, q, k, v, out, lse, indices_2d,
         ctx.softmax_scale, ctx.softcap,
         sink=sink if need_sink else None, sink_layout=ctx.sink_layout,
+        q_block_size=ctx.q_block_size,
     )
     need_q, need_k, need_v = ctx.needs_input_grad[:3]
     return (
@@ -407,7 +429,8 @@ class IndexAttnFunc(torch.autograd.Function):
     pads the bytes and the backward pads the bf16 upcast.
 
     This is the node of a call without sink and max_logits (six inputs, out
-    and lse); IndexAttnSinkFunc below carries those two."""
+    and lse); IndexAttnSinkFunc below carries those two, IndexAttnBlockFunc
+    a q_block_size > 1."""
 
     @staticmethod
     def forward(ctx, q, k, v, indices_2d, softmax_scale, softcap):
@@ -445,6 +468,30 @@ class IndexAttnSinkFunc(torch.autograd.Function):
             ctx, dout, ctx.needs_input_grad[6]
         )
         return _input_grads(IndexAttnSinkFunc, q=dq, k=dk, v=dv, sink=dsink)
+
+
+class IndexAttnBlockFunc(torch.autograd.Function):
+    """The node of an index call with q_block_size > 1: IndexAttnSinkFunc's
+    inputs and outputs (sink may be None, max_logits is None unless asked
+    for) plus q_block_size, which reaches the BLOCK kernels of the forward
+    and of the backward. indices_2d has one row per block of q_block_size q
+    token rows. The per-token nodes above keep their inputs, so a
+    q_block_size = 1 call builds the graph it always built."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, indices_2d, softmax_scale, softcap,
+                sink, sink_layout, return_max_logits, q_block_size):
+        return _index_attn_forward(
+            ctx, q, k, v, indices_2d, softmax_scale, softcap,
+            sink, sink_layout, return_max_logits, q_block_size,
+        )
+
+    @staticmethod
+    def backward(ctx, dout, *_):
+        dq, dk, dv, dsink = _index_attn_backward(
+            ctx, dout, ctx.needs_input_grad[6]
+        )
+        return _input_grads(IndexAttnBlockFunc, q=dq, k=dk, v=dv, sink=dsink)
 
 
 def _flex_flash_attn_backward(
@@ -805,6 +852,26 @@ def flex_flash_attn_func(
     meta.max_logits is the per-head f32 [hq] maximum scaled (softcapped)
     logit over valid slots (-inf if there is none), hq <= 128, and the sink
     logits do not enter it.
+    q_block_size = B > 1 (index path, bf16; k_block_size stays 1): the q rows
+    [b*B, min((b+1)*B, total_q)), with all their hq heads, share the list
+    index_attn_indices.reshape(-1, max_topk)[b], so the tensor holds
+    ceil(total_q / B) lists, not total_q (asserted; the last block may be
+    partial). With KV heads folded into q rows, arranging the rows so that a
+    block belongs to one KV head is the caller's business. The kernels pack a
+    block's B*hq (token, head) rows into their MFMA tiles, gather K/V once
+    per workgroup and not once per token, and the backward issues one dK/dV
+    atomic per gathered row for all the tokens a workgroup holds. softcap,
+    sink (both layouts, dsink), return_max_logits and padded head dims
+    compose with it; a block whose list is all -1 behaves as such a token
+    does. Results agree with the B = 1 call over the lists repeated B times
+    within rounding, not bit for bit (the deferred-max decision is per wave,
+    and packing changes which rows share one). Measured on an MI355X against
+    the per-token kernels over the expanded lists (d 128, topk 2048, 16k
+    tokens; profiles/index_q_block.md): hq 32, B 64 3.9x forward and
+    backward; hq 8, B 16 14.8x forward, 14.2x backward; with hq 128 the
+    tiles are full already and B = 4 is level (1.03x / 1.00x), no shape
+    measured loses. fp8 inputs with q_block_size > 1 are refused. B = 1
+    runs the per-token kernels, unchanged.
 
     On the range path q/k/v may also be all float16: out and the gradients
     come back in fp16, lse / max_logits / dsink math stays f32, and every
@@ -963,14 +1030,30 @@ def flex_flash_attn_func(
             f"index_attn_indices must be 3D (total_q, num_kv_heads, max_topk), "
             f"got shape {tuple(index_attn_indices.shape)}"
         )
-        assert q_block_size == 1 and k_block_size == 1, (
-            "only q_block_size=1 / k_block_size=1 (token granularity) is "
+        assert k_block_size == 1, (
+            "only k_block_size=1 (token granularity on the K side) is "
             "supported for index_attn"
+        )
+        assert q_block_size >= 1, (
+            f"q_block_size must be >= 1, got {q_block_size}"
+        )
+        assert q_block_size == 1 or q.dtype != torch.float8_e4m3fn, (
+            "index_attn with q_block_size > 1 is bf16 only: fp8 inputs are "
+            "not supported with it"
         )
         max_topk = index_attn_indices.shape[2]
         assert max_topk % 64 == 0, (
             f"index_attn max_topk={max_topk} must be a multiple of 64 "
             f"(pad with -1)"
+        )
+        n_q_blocks = -(-q.shape[0] // q_block_size)
+        assert q_block_size == 1 or (
+            index_attn_indices.numel() == n_q_blocks * max_topk
+        ), (
+            f"index_attn_indices has {index_attn_indices.numel() // max_topk} "
+            f"lists; q_block_size={q_block_size} needs ceil(total_q / "
+            f"q_block_size) = ceil({q.shape[0]} / {q_block_size}) = "
+            f"{n_q_blocks}"
         )
         # the differentiable path is taken only when a gradient can flow; the
         # no-grad call below is the plain forward launch
@@ -994,6 +1077,12 @@ def flex_flash_attn_func(
             assert q.shape[1] <= 128, "num_qheads must be <= 128 (reference cap)"
 
         def _index_call(q_, k_, v_):
+            if needs_grad and q_block_size != 1:
+                out_, lse_, ml_ = IndexAttnBlockFunc.apply(
+                    q_, k_, v_, indices_2d, softmax_scale, softcap,
+                    sink, sink_layout, return_max_logits, q_block_size,
+                )
+                return out_, AttnForwardMeta(lse=lse_, max_logits=ml_)
             if needs_grad:
                 if sink is None and not return_max_logits:
                     out_, lse_ = IndexAttnFunc.apply(
@@ -1010,6 +1099,7 @@ def flex_flash_attn_func(
             return _flex_flash_attn_forward_index(
                 q_, k_, v_, indices_2d, softmax_scale, softcap,
                 sink=sink, sink_layout=sink_layout, max_logits=ml_,
+                q_block_size=q_block_size,
             )
 
         d = q.shape[-1]
