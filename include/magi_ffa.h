@@ -667,6 +667,66 @@ typedef struct magi_ffa_index_bwd_block_args {
 int magi_ffa_bwd_index_block(const magi_ffa_index_bwd_block_args* args);
 int magi_ffa_bwd_index_block_args_size(void);
 
+/* k_block_size on the index path (the reference declares it and leaves it
+ * unimplemented): list entries are K BLOCK ids. With Bk = k_block_size, id j
+ * stands for rows [j*Bk, min((j+1)*Bk, total_k)) of k / v as passed
+ * ([total_k, 1, d], hk == 1); -1 is contiguous tail padding as above. When
+ * total_k % Bk != 0 the last block is short; it may sit anywhere in a list and
+ * its missing rows contribute nothing (no logit, no max_logits, no atomic). An
+ * id outside [0, ceil(total_k / Bk)) is handled like an out-of-range row id of
+ * the base entries: loads are clamped, the entry is masked. With KV heads
+ * folded into the row dimension a block is Bk consecutive rows of the tensor;
+ * laying rows out so that a block belongs to one KV head is the caller's
+ * business. Shapes of indices_2d are those of the embedded entry:
+ * [ceil(total_q / q_block_size), max_topk].
+ *
+ * The kernels are KBLOCK instantiations of ffa_index.hip, ffa_index_fp8.hip
+ * and ffa_index_bwd.hip: their k loop runs over row positions
+ * 0 .. count_blocks*Bk, position pos -> list slot pos / Bk, row id*Bk +
+ * pos % Bk; nothing is expanded on the host or into a buffer. Where a staged
+ * group of rows lies inside one block the id is read once per wave and lane
+ * addresses are base + offset. Results agree with the embedded entry over
+ * lists expanded to row ids within rounding, not bit for bit.
+ *   q_block_size  (bf16 entries) as in magi_ffa_index_block_args; 1 runs the
+ *                 per-token kernels' KBLOCK build, > 1 the BLOCK ones'.
+ *   k_block_size  Bk, a power of two >= 2.
+ *   reserved      not read.
+ * Validation is the embedded entry's, same order and codes, all before any
+ * HIP call, with two changes: -4 is max_topk <= 0 or (max_topk * Bk) % 64 != 0
+ * (so Bk = 64 allows any max_topk; a bad Bk is judged as 1 here), and the next
+ * free code is returned for k_block_size not a power of two >= 2 or
+ * max_topk * Bk not fitting int32: -7 for magi_ffa_fwd_index_kblock (after
+ * -1 .. -6), -6 for magi_ffa_fwd_index_fp8_kblock (after -1 .. -5; it embeds
+ * the base struct and has no q_block_size: there is no fp8 q-block kernel),
+ * -6 for magi_ffa_bwd_index_kblock (after -1 .. -5). Then total_q <= 0
+ * returns 0 without a launch. A null struct is -1. */
+typedef struct magi_ffa_index_kblock_args {
+  magi_ffa_index_block_args block;  /* indices_2d entries: K block ids */
+  int32_t k_block_size;             /* Bk: power of two >= 2 */
+  int32_t reserved;
+} magi_ffa_index_kblock_args;
+
+int magi_ffa_fwd_index_kblock(const magi_ffa_index_kblock_args* args);
+int magi_ffa_fwd_index_kblock_args_size(void);
+
+typedef struct magi_ffa_index_fp8_kblock_args {
+  magi_ffa_index_args args;         /* q, k, v: raw e4m3 bytes */
+  int32_t k_block_size;             /* Bk: power of two >= 2 */
+  int32_t reserved;
+} magi_ffa_index_fp8_kblock_args;
+
+int magi_ffa_fwd_index_fp8_kblock(const magi_ffa_index_fp8_kblock_args* args);
+int magi_ffa_fwd_index_fp8_kblock_args_size(void);
+
+typedef struct magi_ffa_index_bwd_kblock_args {
+  magi_ffa_index_bwd_block_args block;
+  int32_t k_block_size;             /* Bk: power of two >= 2 */
+  int32_t reserved;
+} magi_ffa_index_bwd_kblock_args;
+
+int magi_ffa_bwd_index_kblock(const magi_ffa_index_bwd_kblock_args* args);
+int magi_ffa_bwd_index_kblock_args_size(void);
+
 /* Version/identity probe so tests can verify the native library is loaded. */
 int magi_ffa_abi_version(void);
 

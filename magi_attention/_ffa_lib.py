@@ -306,6 +306,36 @@ class MagiFfaIndexBwdBlockArgs(MagiFfaIndexBwdArgs):
     _fields_ = _Q_BLOCK_FIELDS
 
 
+# list entries are ids of blocks of k_block_size K rows: the three *_kblock
+# entries. The C field after k_block_size is `reserved`; the mirrors call it
+# k_reserved because the embedded q-block struct already has that name.
+_K_BLOCK_FIELDS = [
+    ("k_block_size", ctypes.c_int32),  # power of two >= 2
+    ("k_reserved", ctypes.c_int32),
+]
+
+
+class MagiFfaIndexKBlockArgs(MagiFfaIndexBlockArgs):
+    """mirrors magi_ffa_index_kblock_args: magi_ffa_index_block_args embedded
+    first, then the k_block_size of magi_ffa_fwd_index_kblock"""
+
+    _fields_ = _K_BLOCK_FIELDS
+
+
+class MagiFfaIndexFp8KBlockArgs(_MagiFfaIndexArgsFull):
+    """mirrors magi_ffa_index_fp8_kblock_args: the base magi_ffa_index_args
+    (there is no fp8 q-block kernel), then k_block_size"""
+
+    _fields_ = _K_BLOCK_FIELDS
+
+
+class MagiFfaIndexBwdKBlockArgs(MagiFfaIndexBwdBlockArgs):
+    """mirrors magi_ffa_index_bwd_kblock_args: magi_ffa_index_bwd_block_args
+    embedded first, then the k_block_size of magi_ffa_bwd_index_kblock"""
+
+    _fields_ = _K_BLOCK_FIELDS
+
+
 class MagiCorrectArgs(ctypes.Structure):
     _fields_ = [
         ("out1", ctypes.c_void_p),
@@ -343,7 +373,16 @@ def _try_load() -> ctypes.CDLL | None:
             ("magi_ffa_bwd_index_block",
              [ctypes.POINTER(MagiFfaIndexBwdBlockArgs)]),
             ("magi_ffa_bwd_index_block_args_size", []),
-            ("magi_ffa_bwd", [ctypes.POINTER(MagiFfaBwdArgs)]),
+            ("magi_ffa_fwd_index_kblock",
+             [ctypes.POINTER(MagiFfaIndexKBlockArgs)]),
+            ("magi_ffa_fwd_index_kblock_args_size", []),
+            ("magi_ffa_fwd_index_fp8_kblock",
+             [ctypes.POINTER(MagiFfaIndexFp8KBlockArgs)]),
+            ("magi_ffa_fwd_index_fp8_kblock_args_size", []),
+            ("magi_ffa_bwd_index_kblock",
+             [ctypes.POINTER(MagiFfaIndexBwdKBlockArgs)]),
+            ("magi_ffa_bwd_index_kblock_args_size", []),
+            ("magi_ffa_bwd",[ctypes.POINTER(MagiFfaBwdArgs)]),
             ("magi_ffa_bwd_dq", [ctypes.POINTER(MagiFfaBwdArgs)]),
             ("magi_ffa_bwd_dkv", [ctypes.POINTER(MagiFfaBwdArgs)]),
             ("magi_ffa_bwd_dv", [ctypes.POINTER(MagiFfaBwdArgs)]),
@@ -403,6 +442,12 @@ def _try_load() -> ctypes.CDLL | None:
             (MagiFfaIndexBlockArgs, lib.magi_ffa_fwd_index_block_args_size()),
             (MagiFfaIndexBwdBlockArgs,
              lib.magi_ffa_bwd_index_block_args_size()),
+            (MagiFfaIndexKBlockArgs,
+             lib.magi_ffa_fwd_index_kblock_args_size()),
+            (MagiFfaIndexFp8KBlockArgs,
+             lib.magi_ffa_fwd_index_fp8_kblock_args_size()),
+            (MagiFfaIndexBwdKBlockArgs,
+             lib.magi_ffa_bwd_index_kblock_args_size()),
         ]:
             if ctypes.sizeof(cls) != size:
                 raise RuntimeError(

@@ -4,6 +4,8 @@
 //               SPARSE_MAP_ROWS (ffa_fwd, ffa_bwd)
 //   lanes       warp_xor32 (all kernels)
 //   index rows  index_valid_count (index forwards and backward),
+//               kblock_row, kblock_row_uniform, kblock_tile_mask (their
+//               KBLOCK instantiations),
 //               index_sink_lse, index_sink_fold, head_atomic_max
 //               (ffa_index, ffa_index_fp8)
 //   fragments   pack_bf16_pair, fast_exp2, crow, tr16_frag, cframe_to_afrag
@@ -11,7 +13,8 @@
 //   softmax     FP8_MAX_OFFSET, softmax_step_fp8 (ffa_fwd_fp8, ffa_index_fp8)
 //   index host  IdxFwdParams<T>, index_fwd_entry: the one host path of
 //               magi_ffa_fwd_index, magi_ffa_fwd_index_fp8 and
-//               magi_ffa_fwd_index_block; index_waves (the backward too)
+//               magi_ffa_fwd_index_block and the two forward *_kblock
+//               entries; index_waves, kblock_log2 (the backward too)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -103,6 +106,55 @@ DEV_INLINE int index_valid_count(const int* irow, int max_topk) {
     count = lo;
   }
   return count;
+}
+
+// ---- K-block position space (the KBLOCK index kernels, k_block_size = Bk =
+// 1 << lg) ----
+// The list holds K BLOCK ids and the kernels' k loop runs over row positions
+// 0 .. count_blocks * Bk: position pos belongs to list slot pos >> lg and names
+// K row id * Bk + (pos & (Bk - 1)). Nothing is expanded anywhere; a lane turns
+// the positions it stages or masks into rows with the helpers below. They
+// return the row, or -1 where there is none: a negative id (padding), an id
+// past the last block, a row past total_k in the ragged last block. All of it
+// is 32-bit: tk32 = kblock_tk32(total_k), so a row at or beyond 2^31 cannot be
+// named - as with the int32 row ids of the per-token kernels.
+DEV_INLINE int kblock_tk32(long long total_k) {
+  return (int)min(total_k, (long long)INT32_MAX);
+}
+
+// row of offset off (0 <= off < Bk) in block id; (id << lg) stays below 2^31
+// once id has passed the first test, so the unsigned sum cannot wrap
+DEV_INLINE int kblock_row_of(int id, int off, int lg, int tk32) {
+  const unsigned row = ((unsigned)id << lg) + (unsigned)off;
+  return ((unsigned)id <= (unsigned)((tk32 - 1) >> lg) && row < (unsigned)tk32)
+             ? (int)row
+             : -1;
+}
+
+// this lane's own position
+DEV_INLINE int kblock_row(const int* irow, int pos, int lg, int tk32) {
+  return kblock_row_of(irow[pos >> lg], pos & ((1 << lg) - 1), lg, tk32);
+}
+
+// Row of position pos0 + off, pos0 wave-uniform, for a run of n <= Bk
+// positions that starts at pos0 with n | pos0 (n a power of two) and off < n:
+// the run lies in one block, so the id is read once and pinned to an SGPR,
+// and a lane's row is base + its offset - no per-lane index load.
+DEV_INLINE int kblock_row_uniform(const int* irow, int pos0, int off, int lg,
+                                  int tk32) {
+  const int id = __builtin_amdgcn_readfirstlane(irow[pos0 >> lg]);
+  return kblock_row_of(id, (pos0 & ((1 << lg) - 1)) + off, lg, tk32);
+}
+
+// Live mask of the 32-position tile at ns (wave-uniform, 32 | ns): bit i is set
+// when position ns + i is below count and its row exists. Lanes l and l + 32
+// both test position ns + l. The whole wave must be active. Bk >= 32 takes the
+// uniform arm (block-uniform branch).
+DEV_INLINE unsigned kblock_tile_mask(const int* irow, int ns, int lg, int count,
+                                     int tk32, int lo32) {
+  const int row = (lg >= 5) ? kblock_row_uniform(irow, ns, lo32, lg, tk32)
+                            : kblock_row(irow, ns + lo32, lg, tk32);
+  return (unsigned)__ballot(ns + lo32 < count && row >= 0);
 }
 
 // ---- index-attention epilogue helpers (ffa_index.hip, ffa_index_fp8.hip) ----
@@ -401,6 +453,7 @@ struct IdxFwdParams {
   int sink_ssh;
   float* max_logits;  // [hq], null = off
   int q_block;        // BLOCK kernels only: q token rows per index row
+  int kb_lg;          // KBLOCK kernels only: log2(k_block_size)
 };
 
 // Wave count of an index workgroup from the rows that share one index row
@@ -411,23 +464,38 @@ static inline int index_waves(long long rows) {
   return (rows > 64) ? 4 : (rows > 32 ? 2 : 1);
 }
 
+// log2 of a k_block_size, -1 unless it is a power of two >= 2
+static inline int kblock_log2(int32_t kb) {
+  if (kb < 2 || (kb & (kb - 1)) != 0) return -1;
+  return __builtin_ctz((unsigned)kb);
+}
+
 // Body of magi_ffa_fwd_index / magi_ffa_fwd_index_fp8 / _block: checks,
 // params, launch shape and dispatch. launch(D, W, HAS_SOFTCAP, OUT_BF16, grid,
 // block, stream, p) gets the four template arguments as
 // std::integral_constant values and launches its kernel. Nothing before that
 // call touches the HIP runtime. q_block (magi_ffa_fwd_index_block only): q
 // token rows per index row; the grid is then (row blocks, chunks of 32*W
-// packed rows) and launch starts the BLOCK kernels.
+// packed rows) and launch starts the BLOCK kernels. k_block (the *_kblock
+// entries only): K rows per list entry; the lists hold block ids, the
+// alignment rule is on max_topk * k_block_size and a bad size takes the code
+// after the last one of the entry it extends.
 template <class T, class Launch>
 static int index_fwd_entry(const magi_ffa_index_args* a, Launch launch,
-                           const int32_t* q_block = nullptr) {
+                           const int32_t* q_block = nullptr,
+                           const int32_t* k_block = nullptr) {
   if (!a || !a->q || !a->k || !a->v || !a->out || !a->lse || !a->indices_2d)
     return -1;
   if (a->d != 64 && a->d != 128) return -2;
   if (a->hk != 1) return -3;  // kv heads are folded into K rows (magi_ffa.h)
-  if (a->max_topk <= 0 || (a->max_topk & 63) != 0) return -4;
+  // row positions a list spans; a bad k_block_size is judged as 1 here and
+  // refused below
+  const int kb_lg = k_block ? kblock_log2(*k_block) : 0;
+  const long long positions = (long long)a->max_topk << std::max(kb_lg, 0);
+  if (a->max_topk <= 0 || (positions & 63) != 0) return -4;
   if (a->sink && (a->s_sink < 1 || a->s_sink > 8)) return -5;
   if (q_block && *q_block < 1) return -6;
+  if (k_block && (kb_lg < 0 || positions > INT32_MAX)) return q_block ? -7 : -6;
   if (a->total_q <= 0 || a->hq <= 0) return 0;
 
   IdxFwdParams<T> p;
@@ -450,6 +518,7 @@ static int index_fwd_entry(const magi_ffa_index_args* a, Launch launch,
   p.max_logits = a->max_logits;
   // a block longer than q is the one block [0, total_q)
   p.q_block = q_block ? (int)std::min<long long>(*q_block, a->total_q) : 1;
+  p.kb_lg = kb_lg;
 
   // head-block = 32*W rows of the hq (x q_block) that share an index row
   const long long qb = p.q_block;

@@ -33,6 +33,16 @@
 // over expanded lists within rounding, not bit for bit. The default
 // instantiations take the BLOCK = false arm everywhere and keep their code.
 //
+// KBLOCK instantiations (magi_ffa_fwd_index_kblock, k_block_size = Bk, a
+// power of two >= 2), in both BLOCK arms: list entries are K BLOCK ids, block
+// j = rows [j*Bk, min((j+1)*Bk, total_k)). The k loop runs over row positions
+// 0 .. count_blocks*Bk (ffa_device.h: kblock_row), nothing is expanded. A
+// staged 1-KB group inside one block (Bk >= 1024 / row bytes) takes one
+// wave-uniform id pinned to an SGPR plus lane offsets; smaller blocks index
+// the list per lane by the shifted slot. The per-tile live mask (one ballot)
+// replaces `position < count`: it also drops rows a ragged or out-of-range
+// block does not have, and only an all-live tile takes the unmasked path.
+//
 // Epilogue extras, both off (null pointers, block-uniform branches, k loop
 // untouched, out/lse bit-identical) unless asked for:
 //   - attention sink: a lane owns one query head, so it loads that head's
@@ -52,7 +62,8 @@
 
 #define IDX_BN 32  // k rows per inner MFMA tile
 
-template <int D, bool HAS_SOFTCAP, bool OUT_BF16, int WAVES, bool BLOCK = false>
+template <int D, bool HAS_SOFTCAP, bool OUT_BF16, int WAVES, bool BLOCK = false,
+          bool KBLOCK = false>
 __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     IdxFwdParams<bf16_t> p) {
   constexpr int DF = D / 16;
@@ -80,7 +91,11 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
   const int hi = lane >> 5;
 
   const int* irow = p.idx2d + tok * (long long)p.max_topk;
-  const int count = index_valid_count(irow, p.max_topk);
+  // KBLOCK: valid block ids -> row positions (max_topk << kb_lg fits an int,
+  // checked by the host entry)
+  const int count = KBLOCK ? index_valid_count(irow, p.max_topk) << p.kb_lg
+                           : index_valid_count(irow, p.max_topk);
+  const int tk32 = KBLOCK ? kblock_tk32(p.total_k) : 0;  // see kblock_row_of
   if (__builtin_expect(count == 0, 0)) {
     // out zero-init + lse -inf preset by the host; with a sink the row's
     // softmax mass is the sink's alone: lse = lse_sink, out stays 0
@@ -153,13 +168,26 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
   // Gathered stage: global row = irow[position], clamped for safety. The
   // staged positions never exceed max_topk-1 (64 | max_topk and the loop
   // rounds count up to 64).
+  // KBLOCK: positions instead of slots, bounded by max_topk << kb_lg in the
+  // same way (64 divides it). A 1-KB glds group is ROWS_PER_GLDS consecutive
+  // positions at a multiple of ROWS_PER_GLDS, so from Bk = ROWS_PER_GLDS on it
+  // lies in one block: the id is wave-uniform, read once, and lanes add their
+  // row offset. Smaller blocks take their id per lane by the shifted slot.
+  // Block-uniform branch; rows past total_k (ragged block) clamp like pads.
   auto stage_glds = [&](int buf, int n0x) {
 #pragma unroll
     for (int gi = 0; gi < GLDS_PER_WAVE; ++gi) {
       const int r0 = (IDX_KITER / WAVES) * wave + ROWS_PER_GLDS * gi;
       const int r = r0 + lane / (ROWB / 16);
       const int c = lane % (ROWB / 16);
-      long long kr = irow[n0x + r];
+      long long kr;
+      if (!KBLOCK)
+        kr = irow[n0x + r];
+      else if ((1 << p.kb_lg) >= ROWS_PER_GLDS)
+        kr = kblock_row_uniform(irow, n0x + r0, lane / (ROWB / 16), p.kb_lg,
+                                tk32);
+      else
+        kr = kblock_row(irow, n0x + r, p.kb_lg, tk32);
       if (kr < 0 || kr >= p.total_k) kr = 0;  // pad/garbage: any in-bounds row
       const int cs = c ^ ((r & SW32M) << 1);
       const int csw = cs * 8;
@@ -188,7 +216,14 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
     }
 
     // ---- mask (position >= count) + scale into exp2 domain ----
-    const bool interior = (q0 + 31 < nrows) && (ns + IDX_BN <= count);
+    // KBLOCK: bit i of vmask = position ns + i is below count and its row
+    // exists; a tile that touches a ragged or out-of-range block is not
+    // interior, wherever it sits in the list
+    const unsigned vmask =
+        KBLOCK ? kblock_tile_mask(irow, ns, p.kb_lg, count, tk32, lo32)
+               : 0u;
+    const bool interior = (q0 + 31 < nrows) &&
+                          (KBLOCK ? vmask == ~0u : ns + IDX_BN <= count);
     float t[16];
     float mx = -INFINITY;
     if (interior) {
@@ -203,7 +238,8 @@ __global__ __launch_bounds__(64 * WAVES, 8 / WAVES) void ffa_index_fwd_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int kk = ns + crow(r, hi);
-        const bool ok = qvalid && (kk < count);
+        const bool ok =
+            qvalid && (KBLOCK ? ((vmask >> crow(r, hi)) & 1u) != 0 : kk < count);
         float sv = s[r];
         if (HAS_SOFTCAP) sv = tanhf(sv * cap_pre);
         t[r] = ok ? sv * sl2 : -INFINITY;
@@ -359,4 +395,33 @@ extern "C" int magi_ffa_fwd_index_block(const magi_ffa_index_block_args* a) {
 
 extern "C" int magi_ffa_fwd_index_block_args_size(void) {
   return (int)sizeof(magi_ffa_index_block_args);
+}
+
+// k_block_size entry: the KBLOCK instantiations, list entries are K block ids.
+// q_block_size 1 runs the per-token arm, anything else the BLOCK arm.
+extern "C" int magi_ffa_fwd_index_kblock(const magi_ffa_index_kblock_args* a) {
+  if (!a) return -1;
+  if (a->block.q_block_size == 1)
+    return index_fwd_entry<bf16_t>(
+        &a->block.args,
+        [](auto D, auto W, auto SC, auto OB, dim3 grid, dim3 block,
+           hipStream_t stream, const IdxFwdParams<bf16_t>& p) {
+          hipLaunchKernelGGL(
+              (ffa_index_fwd_kernel<D(), SC(), OB(), W(), false, true>), grid,
+              block, 0, stream, p);
+        },
+        &a->block.q_block_size, &a->k_block_size);
+  return index_fwd_entry<bf16_t>(
+      &a->block.args,
+      [](auto D, auto W, auto SC, auto OB, dim3 grid, dim3 block,
+         hipStream_t stream, const IdxFwdParams<bf16_t>& p) {
+        hipLaunchKernelGGL(
+            (ffa_index_fwd_kernel<D(), SC(), OB(), W(), true, true>), grid,
+            block, 0, stream, p);
+      },
+      &a->block.q_block_size, &a->k_block_size);
+}
+
+extern "C" int magi_ffa_fwd_index_kblock_args_size(void) {
+  return (int)sizeof(magi_ffa_index_kblock_args);
 }

@@ -38,6 +38,14 @@
 // per row; phase 2 reduces over rows of several tokens, so one atomic per
 // (workgroup, gathered row) replaces one per token. The LDS images are per
 // row and keep their sizes (the static_assert below covers every build).
+//
+// KBLOCK instantiations (magi_ffa_bwd_index_kblock, k_block_size = Bk), in
+// both BLOCK arms: list entries are K block ids and the tile loop runs over
+// row positions (ffa_device.h: kblock_row / kblock_row_uniform). The per-tile
+// gid[] holds K rows, -1 for padding and for rows a ragged or out-of-range
+// block does not have, so those enter no P, no dS and no atomic. From Bk = 32
+// on a tile is one block: one pinned id replaces the four int4 index loads.
+// The default and BLOCK instantiations take the KBLOCK = false arms.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -64,9 +72,11 @@ struct IdxBwdParams {
   float softcap;
   long long total_q, total_k;
   int q_block;  // BLOCK kernels only: q token rows per index row
+  int kb_lg;    // KBLOCK kernels only: log2(k_block_size)
 };
 
-template <int D, bool HAS_SOFTCAP, int WAVES, bool BLOCK = false>
+template <int D, bool HAS_SOFTCAP, int WAVES, bool BLOCK = false,
+          bool KBLOCK = false>
 __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
     IdxBwdParams p) {
   constexpr int DF = D / 16;
@@ -92,7 +102,11 @@ __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
   const int hi = lane >> 5;
 
   const int* irow = p.idx2d + tok * (long long)p.max_topk;
-  const int count = index_valid_count(irow, p.max_topk);
+  // KBLOCK: valid block ids -> row positions (max_topk << kb_lg fits an int,
+  // checked by the host entry)
+  const int count = KBLOCK ? index_valid_count(irow, p.max_topk) << p.kb_lg
+                           : index_valid_count(irow, p.max_topk);
+  const int tk32 = KBLOCK ? kblock_tk32(p.total_k) : 0;  // see kblock_row_of
   if (count == 0) return;  // dq zero-init by the host; no dk/dv contribution
   // a partial last block may leave whole workgroups without a row
   if (BLOCK && h0 >= nrows) return;
@@ -193,7 +207,17 @@ __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
     for (int gi = 0; gi < GLDS_PER_WAVE; ++gi) {
       const int r0 = (IDXB_BN / WAVES) * wave + ROWS_PER_GLDS * gi;
       const int r = r0 + g_r;
-      long long kr = irow[n0x + r];
+      // KBLOCK: positions, bounded by max_topk << kb_lg in the same way. From
+      // Bk = ROWS_PER_GLDS on a 1-KB group lies in one block: one wave-uniform
+      // id plus the lane's row offset; smaller blocks take their id per lane
+      // by the shifted slot (block-uniform branch)
+      long long kr;
+      if (!KBLOCK)
+        kr = irow[n0x + r];
+      else if ((1 << p.kb_lg) >= ROWS_PER_GLDS)
+        kr = kblock_row_uniform(irow, n0x + r0, g_r, p.kb_lg, tk32);
+      else
+        kr = kblock_row(irow, n0x + r, p.kb_lg, tk32);
       if (kr < 0 || kr >= p.total_k) kr = 0;
       const int cs = g_c ^ ((r & SW32M) << 1);
       __builtin_amdgcn_global_load_lds(
@@ -242,14 +266,36 @@ __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
 
     // global ids of this lane's 16 C-fragment rows (crow(r, hi) = 8*(r>>2)
     // + 4*hi + (r&3)): four aligned int4 loads, shared by both phases
+    // KBLOCK: the K ROW of each of the 16 positions, -1 where the position is
+    // padding or its row does not exist (ragged last block, id out of range),
+    // so the two predicates below hold for it as they stand and such rows
+    // issue no atomic. A live row is below total_k, hence fits an int. From
+    // Bk = 32 on the tile lies in one block: one pinned id plus offsets.
+    // Below that, positions come in aligned pairs inside one block (Bk >= 2):
+    // one id load per pair.
     int gid[16];
+    if (!KBLOCK) {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int4 v4 = *(const int4*)(irow + ns + 8 * g + 4 * hi);
-      gid[4 * g + 0] = v4.x;
-      gid[4 * g + 1] = v4.y;
-      gid[4 * g + 2] = v4.z;
-      gid[4 * g + 3] = v4.w;
+      for (int g = 0; g < 4; ++g) {
+        const int4 v4 = *(const int4*)(irow + ns + 8 * g + 4 * hi);
+        gid[4 * g + 0] = v4.x;
+        gid[4 * g + 1] = v4.y;
+        gid[4 * g + 2] = v4.z;
+        gid[4 * g + 3] = v4.w;
+      }
+    } else {
+      const bool one_block = p.kb_lg >= 5;  // block-uniform
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        const int off = crow(r, hi);  // even: off, off + 1 share a block
+        const int row =
+            one_block ? kblock_row_uniform(irow, ns, off, p.kb_lg, tk32)
+                      : kblock_row(irow, ns + off, p.kb_lg, tk32);
+        // the pair's second row can be the first one past total_k
+        gid[r] = (ns + off < count) ? row : -1;
+        gid[r + 1] =
+            (ns + off + 1 < count && row >= 0 && row + 1 < tk32) ? row + 1 : -1;
+      }
     }
 
     const char* lkb = lds_k(cur);
@@ -365,32 +411,40 @@ __global__ __launch_bounds__(64 * WAVES) void ffa_index_bwd_kernel(
 // ------------------------------------------------------------------
 // launcher
 // ------------------------------------------------------------------
-template <int D, int W, bool BLOCK>
+template <int D, int W, bool BLOCK, bool KBLOCK>
 static int launch_index_bwd(const IdxBwdParams& p, dim3 grid,
                             hipStream_t stream) {
   dim3 block(64 * W);
   if (p.softcap > 0.f)
-    hipLaunchKernelGGL((ffa_index_bwd_kernel<D, true, W, BLOCK>), grid, block,
-                       0, stream, p);
+    hipLaunchKernelGGL((ffa_index_bwd_kernel<D, true, W, BLOCK, KBLOCK>), grid,
+                       block, 0, stream, p);
   else
-    hipLaunchKernelGGL((ffa_index_bwd_kernel<D, false, W, BLOCK>), grid, block,
-                       0, stream, p);
+    hipLaunchKernelGGL((ffa_index_bwd_kernel<D, false, W, BLOCK, KBLOCK>), grid,
+                       block, 0, stream, p);
   return (int)hipGetLastError();
 }
 
 // Body of magi_ffa_bwd_index (q_block null: the default kernels, one index
-// row per token) and magi_ffa_bwd_index_block (the BLOCK kernels, one index
-// row per *q_block token rows).
-template <bool BLOCK>
+// row per token), magi_ffa_bwd_index_block (the BLOCK kernels, one index
+// row per *q_block token rows) and magi_ffa_bwd_index_kblock (the KBLOCK
+// kernels of either arm: list entries are ids of blocks of *k_block K rows,
+// the alignment rule is on max_topk * k_block_size, a bad size is -6).
+template <bool BLOCK, bool KBLOCK = false>
 static int index_bwd_entry(const magi_ffa_index_bwd_args* a,
-                           const int32_t* q_block) {
+                           const int32_t* q_block,
+                           const int32_t* k_block = nullptr) {
   if (!a || !a->dout || !a->q || !a->k || !a->v || !a->lse || !a->dpsum ||
       !a->indices_2d || !a->dq || !a->dk || !a->dv)
     return -1;
   if (a->d != 64 && a->d != 128) return -2;
   if (a->hk != 1) return -3;  // kv heads are folded into K rows (see header)
-  if (a->max_topk <= 0 || (a->max_topk & 63) != 0) return -4;
+  // row positions a list spans; a bad k_block_size is judged as 1 here and
+  // refused below
+  const int kb_lg = k_block ? kblock_log2(*k_block) : 0;
+  const long long positions = (long long)a->max_topk << std::max(kb_lg, 0);
+  if (a->max_topk <= 0 || (positions & 63) != 0) return -4;
   if (q_block && *q_block < 1) return -5;
+  if (k_block && (kb_lg < 0 || positions > INT32_MAX)) return -6;
   if (a->total_q <= 0 || a->total_k <= 0 || a->hq <= 0) return 0;
 
   IdxBwdParams p;
@@ -412,6 +466,7 @@ static int index_bwd_entry(const magi_ffa_index_bwd_args* a,
   p.total_k = a->total_k;
   // a block longer than q is the one block [0, total_q)
   p.q_block = q_block ? (int)std::min<long long>(*q_block, a->total_q) : 1;
+  p.kb_lg = kb_lg;
 
   // head-block = 32*W rows of the hq (x q_block) that share an index row, the
   // rule of index_fwd_entry (ffa_device.h)
@@ -423,13 +478,13 @@ static int index_bwd_entry(const magi_ffa_index_bwd_args* a,
             (unsigned)((rows + span - 1) / span), 1);
   hipStream_t stream = (hipStream_t)a->stream;
   if (a->d == 64) {
-    if (w == 4) return launch_index_bwd<64, 4, BLOCK>(p, grid, stream);
-    if (w == 2) return launch_index_bwd<64, 2, BLOCK>(p, grid, stream);
-    return launch_index_bwd<64, 1, BLOCK>(p, grid, stream);
+    if (w == 4) return launch_index_bwd<64, 4, BLOCK, KBLOCK>(p, grid, stream);
+    if (w == 2) return launch_index_bwd<64, 2, BLOCK, KBLOCK>(p, grid, stream);
+    return launch_index_bwd<64, 1, BLOCK, KBLOCK>(p, grid, stream);
   }
-  if (w == 4) return launch_index_bwd<128, 4, BLOCK>(p, grid, stream);
-  if (w == 2) return launch_index_bwd<128, 2, BLOCK>(p, grid, stream);
-  return launch_index_bwd<128, 1, BLOCK>(p, grid, stream);
+  if (w == 4) return launch_index_bwd<128, 4, BLOCK, KBLOCK>(p, grid, stream);
+  if (w == 2) return launch_index_bwd<128, 2, BLOCK, KBLOCK>(p, grid, stream);
+  return launch_index_bwd<128, 1, BLOCK, KBLOCK>(p, grid, stream);
 }
 
 extern "C" int magi_ffa_bwd_index(const magi_ffa_index_bwd_args* a) {
@@ -444,5 +499,20 @@ extern "C" int magi_ffa_bwd_index_block(
 
 extern "C" int magi_ffa_bwd_index_block_args_size(void) {
   return (int)sizeof(magi_ffa_index_bwd_block_args);
+}
+
+// q_block_size 1 runs the per-token arm, anything else the BLOCK arm
+extern "C" int magi_ffa_bwd_index_kblock(
+    const magi_ffa_index_bwd_kblock_args* a) {
+  if (!a) return -1;
+  if (a->block.q_block_size == 1)
+    return index_bwd_entry<false, true>(&a->block.args, &a->block.q_block_size,
+                                        &a->k_block_size);
+  return index_bwd_entry<true, true>(&a->block.args, &a->block.q_block_size,
+                                     &a->k_block_size);
+}
+
+extern "C" int magi_ffa_bwd_index_kblock_args_size(void) {
+  return (int)sizeof(magi_ffa_index_bwd_kblock_args);
 }
 

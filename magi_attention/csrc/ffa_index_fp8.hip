@@ -57,8 +57,16 @@ using i64x2 = __attribute__((ext_vector_type(2))) long;
 // the exp2/pack working set + the V rows in flight), so they ask for 2
 // waves/SIMD (256 registers); a 4 waves/SIMD bound (128) spills. D=64 fits
 // 128 registers at 2 and 4 waves per workgroup.
-template <int D, bool HAS_SOFTCAP, bool OUT_BF16, int WAVES>
-__global__ __launch_bounds__(64 * WAVES, (D > 64 || WAVES < 2) ? 2 : 4) void
+//
+// KBLOCK instantiations (magi_ffa_fwd_index_fp8_kblock, k_block_size = Bk):
+// list entries are K block ids and the k loop runs over row positions, as in
+// ffa_index.hip (helpers and the position map in ffa_device.h). The default
+// instantiations take the KBLOCK = false arm everywhere and keep their code.
+template <int D, bool HAS_SOFTCAP, bool OUT_BF16, int WAVES, bool KBLOCK = false>
+// The D=64 KBLOCK builds sit one register over the 128 of the 4 waves/SIMD
+// bound (1 VGPR spilled), so they take the 2 waves/SIMD bound as D=128 does.
+__global__ __launch_bounds__(64 * WAVES,
+                             (D > 64 || WAVES < 2 || KBLOCK) ? 2 : 4) void
 ffa_index_fwd_fp8_kernel(IdxFwdParams<u8> p) {
   constexpr int DF = D / 16;  // 16-deep MFMAs per QK chain
   constexpr int DT = D / 32;
@@ -72,7 +80,11 @@ ffa_index_fwd_fp8_kernel(IdxFwdParams<u8> p) {
   const int hi = lane >> 5;
 
   const int* irow = p.idx2d + tok * (long long)p.max_topk;
-  const int count = index_valid_count(irow, p.max_topk);
+  // KBLOCK: valid block ids -> row positions (max_topk << kb_lg fits an int,
+  // checked by the host entry)
+  const int count = KBLOCK ? index_valid_count(irow, p.max_topk) << p.kb_lg
+                           : index_valid_count(irow, p.max_topk);
+  const int tk32 = KBLOCK ? kblock_tk32(p.total_k) : 0;  // see kblock_row_of
   if (__builtin_expect(count == 0, 0)) {
     // out zero-init + lse -inf preset by the host; with a sink the row's
     // softmax mass is the sink's alone: lse = lse_sink, out stays 0
@@ -137,13 +149,23 @@ ffa_index_fwd_fp8_kernel(IdxFwdParams<u8> p) {
   // Gathered stage: global row = irow[position], clamped for safety. The
   // staged positions never exceed max_topk-1 (64 | max_topk and the loop
   // rounds count up to KITER <= 64). K goes LDS-direct, V to registers.
+  // KBLOCK: positions bounded by max_topk << kb_lg in the same way. From
+  // Bk = ROWS_PER_GLDS on a 1-KB group lies in one block: one wave-uniform id
+  // plus the lane's row offset; smaller blocks take their id per lane by the
+  // shifted slot (block-uniform branch). Rows past total_k clamp like pads.
   auto stage_issue = [&](int buf, int n0x) {
 #pragma unroll
     for (int gi = 0; gi < GLDS_PER_WAVE; ++gi) {
       const int r0 = (KITER / WAVES) * wave + ROWS_PER_GLDS * gi;
       const int r = r0 + lane / CPR;
       const int c = lane % CPR;
-      long long kr = irow[n0x + r];
+      long long kr;
+      if (!KBLOCK)
+        kr = irow[n0x + r];
+      else if ((1 << p.kb_lg) >= ROWS_PER_GLDS)
+        kr = kblock_row_uniform(irow, n0x + r0, lane / CPR, p.kb_lg, tk32);
+      else
+        kr = kblock_row(irow, n0x + r, p.kb_lg, tk32);
       if (kr < 0 || kr >= p.total_k) kr = 0;  // pad/garbage: any in-bounds row
       const int cs = c ^ kswz(r);
       __builtin_amdgcn_global_load_lds(
@@ -182,7 +204,13 @@ ffa_index_fwd_fp8_kernel(IdxFwdParams<u8> p) {
     }
 
     // ---- mask (position >= count) + scale into exp2 domain ----
-    const bool interior = (q0 + 31 < p.hq) && (ns + IDX8_BN <= count);
+    // KBLOCK: bit i of vmask = position ns + i is below count and its row
+    // exists; a tile that touches a ragged block is not interior
+    const unsigned vmask =
+        KBLOCK ? kblock_tile_mask(irow, ns, p.kb_lg, count, tk32, lo32)
+               : 0u;
+    const bool interior = (q0 + 31 < p.hq) &&
+                          (KBLOCK ? vmask == ~0u : ns + IDX8_BN <= count);
     float t[16];
     float mx = -INFINITY;
     if (interior) {
@@ -197,7 +225,8 @@ ffa_index_fwd_fp8_kernel(IdxFwdParams<u8> p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int kk = ns + crow(r, hi);
-        const bool ok = qvalid && (kk < count);
+        const bool ok =
+            qvalid && (KBLOCK ? ((vmask >> crow(r, hi)) & 1u) != 0 : kk < count);
         float sv = s[r];
         if (HAS_SOFTCAP) sv = tanhf(sv * cap_pre);
         t[r] = ok ? sv * sl2 : -INFINITY;
@@ -295,4 +324,23 @@ extern "C" int magi_ffa_fwd_index_fp8(const magi_ffa_index_args* a) {
         hipLaunchKernelGGL((ffa_index_fwd_fp8_kernel<D(), SC(), OB(), W()>),
                            grid, block, 0, stream, p);
       });
+}
+
+// k_block_size entry: the KBLOCK instantiations, list entries are K block ids
+extern "C" int magi_ffa_fwd_index_fp8_kblock(
+    const magi_ffa_index_fp8_kblock_args* a) {
+  if (!a) return -1;
+  return index_fwd_entry<u8>(
+      &a->args,
+      [](auto D, auto W, auto SC, auto OB, dim3 grid, dim3 block,
+         hipStream_t stream, const IdxFwdParams<u8>& p) {
+        hipLaunchKernelGGL(
+            (ffa_index_fwd_fp8_kernel<D(), SC(), OB(), W(), true>), grid,
+            block, 0, stream, p);
+      },
+      nullptr, &a->k_block_size);
+}
+
+extern "C" int magi_ffa_fwd_index_fp8_kblock_args_size(void) {
+  return (int)sizeof(magi_ffa_index_fp8_kblock_args);
 }

@@ -432,16 +432,25 @@ def run_bwd(args, q_ranges, k_ranges, attn_type_map, device, *,
 # ---------------- index attention ----------------
 def fwd_index(q, k, v, out, lse, indices_2d, softmax_scale, softcap, *,
               sink_f=None, s_sink=0, sink_ssh=False, max_logits=None,
-              q_block_size=1) -> None:
+              q_block_size=1, k_block_size=1) -> None:
     """Index (token-gather) forward into (out bf16, lse): the bf16 or the fp8
     entry by q.dtype. sink_f / s_sink come from _check_sink. q_block_size > 1
     (bf16): indices_2d has one row per block of that many q token rows and the
-    BLOCK kernels of magi_ffa_fwd_index_block run; 1 is today's entry."""
+    BLOCK kernels of magi_ffa_fwd_index_block run; 1 is today's entry.
+    k_block_size > 1: the entries of indices_2d are ids of blocks of that many
+    K rows and the KBLOCK kernels of the *_kblock entries run; 1 is today's
+    entries."""
     tq, hq, d = q.shape
     tk, hk, _ = k.shape
     block = q_block_size != 1
     assert not (block and q.dtype == _FP8), "no fp8 index kernel for q_block_size > 1"
-    args = (_ffa_lib.MagiFfaIndexBlockArgs if block else _ffa_lib.MagiFfaIndexArgs)(
+    kblock = k_block_size != 1
+    if kblock:
+        cls = (_ffa_lib.MagiFfaIndexFp8KBlockArgs if q.dtype == _FP8
+               else _ffa_lib.MagiFfaIndexKBlockArgs)
+    else:
+        cls = _ffa_lib.MagiFfaIndexBlockArgs if block else _ffa_lib.MagiFfaIndexArgs
+    args = cls(
         q=ptr(q), k=ptr(k), v=ptr(v), out=ptr(out), lse=ptr(lse),
         indices_2d=ptr(indices_2d),
         total_q=tq, total_k=tk, max_topk=indices_2d.shape[1],
@@ -452,6 +461,16 @@ def fwd_index(q, k, v, out, lse, indices_2d, softmax_scale, softcap, *,
         sink_ssh=int(sink_ssh), max_logits=ptr(max_logits),
     )
     lib = _ffa_lib.lib()
+    if kblock:
+        args.k_block_size = k_block_size
+        if q.dtype == _FP8:
+            check(lib.magi_ffa_fwd_index_fp8_kblock(args),
+                  "magi_ffa_fwd_index_fp8_kblock")
+        else:
+            args.q_block_size = q_block_size
+            check(lib.magi_ffa_fwd_index_kblock(args),
+                  "magi_ffa_fwd_index_kblock")
+        return
     if block:
         args.q_block_size = q_block_size
         check(lib.magi_ffa_fwd_index_block(args), "magi_ffa_fwd_index_block")
@@ -462,16 +481,19 @@ def fwd_index(q, k, v, out, lse, indices_2d, softmax_scale, softcap, *,
 
 def bwd_index(dout, q, k, v, out, lse, indices_2d, dq, dk, dv,
               softmax_scale, softcap, *, sink=None, sink_layout="sh",
-              q_block_size=1):
+              q_block_size=1, k_block_size=1):
     """Index backward: dpsum preprocess, the gather/scatter kernel into
     (dq, dk, dv) and, with a sink, its gradient; returns that or None.
-    q_block_size as in fwd_index (magi_ffa_bwd_index_block); the preprocess
-    and dsink are row-wise and do not see it."""
+    q_block_size and k_block_size as in fwd_index (magi_ffa_bwd_index_block,
+    magi_ffa_bwd_index_kblock); the preprocess and dsink are row-wise and do
+    not see them."""
     tq, hq, d = q.shape
     tk, hk, _ = k.shape
     dpsum = bwd_dpsum(dout, out)
     block = q_block_size != 1
-    args = (_ffa_lib.MagiFfaIndexBwdBlockArgs if block
+    kblock = k_block_size != 1
+    args = (_ffa_lib.MagiFfaIndexBwdKBlockArgs if kblock
+            else _ffa_lib.MagiFfaIndexBwdBlockArgs if block
             else _ffa_lib.MagiFfaIndexBwdArgs)(
         dout=ptr(dout), q=ptr(q), k=ptr(k), v=ptr(v), lse=ptr(lse),
         dpsum=ptr(dpsum), indices_2d=ptr(indices_2d),
@@ -481,7 +503,12 @@ def bwd_index(dout, q, k, v, out, lse, indices_2d, dq, dk, dv,
         softmax_scale=softmax_scale, softcap=softcap,
         stream=current_stream_ptr(),
     )
-    if block:
+    if kblock:
+        args.q_block_size = q_block_size
+        args.k_block_size = k_block_size
+        check(_ffa_lib.lib().magi_ffa_bwd_index_kblock(args),
+              "magi_ffa_bwd_index_kblock")
+    elif block:
         args.q_block_size = q_block_size
         check(_ffa_lib.lib().magi_ffa_bwd_index_block(args),
               "magi_ffa_bwd_index_block")

@@ -224,6 +224,7 @@ def _flex_flash_attn_forward_index(
     sink_layout: str = "sh",
     max_logits: Optional[torch.Tensor] = None,
     q_block_size: int = 1,
+    k_block_size: int = 1,
 ) -> tuple[torch.Tensor, AttnForwardMeta]:
     """Index-attention (token-gather) forward: the reference's
     index_attn_indices direct-to-kernel path (flex_flash_attn.py:1358-1390).
@@ -235,6 +236,12 @@ def _flex_flash_attn_forward_index(
     q_block_size = B > 1 (bf16 only): indices_2d is [ceil(total_q / B),
     max_topk] and row b serves q token rows [b*B, min((b+1)*B, total_q)); the
     BLOCK kernels pack a block's B*hq (token, head) rows into their tiles.
+
+    k_block_size = Bk > 1 (a power of two; bf16 with any q_block_size, fp8
+    with q_block_size 1): the entries of indices_2d are K BLOCK ids, id j =
+    rows [j*Bk, min((j+1)*Bk, total_k)) of k / v, and (max_topk * Bk) % 64 == 0
+    replaces 64 | max_topk. The KBLOCK kernels walk row positions and form the
+    rows themselves; nothing is expanded here.
 
     q/k/v are all bf16 (csrc/ffa_index.hip) or all fp8-e4m3
     (csrc/ffa_index_fp8.hip: raw e4m3 bytes, no descale factors, the fp8
@@ -265,6 +272,7 @@ def _flex_flash_attn_forward_index(
         "index_attn with q_block_size > 1 is bf16 only: there is no fp8 "
         "kernel for it"
     )
+    _check_k_block_size(k_block_size, indices_2d.shape[1])
     n_blocks = -(-tq // q_block_size)
     assert indices_2d.shape[0] == n_blocks, (
         f"indices_2d rows ({indices_2d.shape[0]}) must match q token rows "
@@ -288,8 +296,28 @@ def _flex_flash_attn_forward_index(
         q, k, v, out, lse, indices_2d, softmax_scale, softcap,
         sink_f=sink_f, s_sink=s_sink, sink_ssh=sink_layout == "ssh",
         max_logits=max_logits, q_block_size=q_block_size,
+        k_block_size=k_block_size,
     )
     return out, AttnForwardMeta(lse=lse, max_logits=max_logits)
+
+
+def _check_k_block_size(k_block_size: int, max_topk: int) -> None:
+    """the index path's rules for k_block_size and the list length: 1 keeps
+    64 | max_topk; Bk > 1 is a power of two with (max_topk * Bk) % 64 == 0 and
+    max_topk * Bk inside int32 (the kernels' position space)"""
+    assert k_block_size >= 1 and k_block_size & (k_block_size - 1) == 0, (
+        f"index_attn k_block_size must be a power of two, got {k_block_size}"
+    )
+    assert (max_topk * k_block_size) % 64 == 0, (
+        f"index_attn max_topk={max_topk} must be a multiple of 64 "
+        f"(pad with -1)" if k_block_size == 1 else
+        f"index_attn max_topk * k_block_size = {max_topk} * {k_block_size} "
+        f"must be a multiple of 64 (pad the lists with -1)"
+    )
+    assert max_topk * k_block_size < 2 ** 31, (
+        f"index_attn max_topk * k_block_size = {max_topk} * {k_block_size} "
+        f"must fit int32"
+    )
 
 
 def _index_head_dim_pad(d: int) -> int:
@@ -325,13 +353,16 @@ def _flex_flash_attn_backward_index(
     sink: Optional[torch.Tensor] = None,
     sink_layout: str = "sh",
     q_block_size: int = 1,
+    k_block_size: int = 1,
 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
     """Index-attention backward (csrc/ffa_index_bwd.hip): dpsum preprocess,
     then one gather/scatter kernel. Returns (dq bf16, dk fp32, dv fp32, dsink):
     dq has a single owner per row and is stored directly; dk/dv are fp32
     accumulators the kernel scatters into with atomic adds (not deterministic).
     q_block_size as in the forward: one atomic then serves all the tokens of
-    a workgroup's chunk of the block.
+    a workgroup's chunk of the block. k_block_size as in the forward: the
+    lists hold K block ids, and rows a ragged last block does not have get no
+    atomic.
 
     With a sink, lse is the sink-corrected lse the forward saved and out the
     sink-scaled out, so the kernel's recomputed P and dpsum = rowsum(dO * O)
@@ -349,15 +380,16 @@ def _flex_flash_attn_backward_index(
     dsink = _ffa_launch.bwd_index(
         dout, q, k, v, out, lse, indices_2d, dq, dk, dv,
         softmax_scale, softcap, sink=sink, sink_layout=sink_layout,
-        q_block_size=q_block_size,
+        q_block_size=q_block_size, k_block_size=k_block_size,
     )
     return dq, dk, dv, dsink
 
 
 def _index_attn_forward(ctx, q, k, v, indices_2d, softmax_scale, softcap,
-                        sink, sink_layout, return_max_logits, q_block_size=1):
-    """forward shared by IndexAttnFunc, IndexAttnSinkFunc and
-    IndexAttnBlockFunc"""
+                        sink, sink_layout, return_max_logits, q_block_size=1,
+                        k_block_size=1):
+    """forward shared by IndexAttnFunc, IndexAttnSinkFunc, IndexAttnBlockFunc
+    and IndexAttnKBlockFunc"""
     d = q.shape[-1]
     pad = _index_head_dim_pad(d) if q.dtype == torch.float8_e4m3fn else 0
     max_logits = (_ffa_launch.new_max_logits(q.shape[1], q.device)
@@ -366,10 +398,11 @@ def _index_attn_forward(ctx, q, k, v, indices_2d, softmax_scale, softcap,
         _pad_head_dim(q, pad), _pad_head_dim(k, pad), _pad_head_dim(v, pad),
         indices_2d, softmax_scale, softcap,
         sink=sink, sink_layout=sink_layout, max_logits=max_logits,
-        q_block_size=q_block_size,
+        q_block_size=q_block_size, k_block_size=k_block_size,
     )
     ctx.save_for_backward(q, k, v, out, meta.lse, indices_2d, sink)
     ctx.q_block_size = q_block_size
+    ctx.k_block_size = k_block_size
     ctx.softmax_scale = softmax_scale
     ctx.softcap = softcap
     ctx.pad = pad
@@ -397,7 +430,7 @@ def _index_attn_backward(ctx, dout, need_sink):
         dout, q, k, v, out, lse, indices_2d,
         ctx.softmax_scale, ctx.softcap,
         sink=sink if need_sink else None, sink_layout=ctx.sink_layout,
-        q_block_size=ctx.q_block_size,
+        q_block_size=ctx.q_block_size, k_block_size=ctx.k_block_size,
     )
     need_q, need_k, need_v = ctx.needs_input_grad[:3]
     return (
@@ -492,6 +525,32 @@ class IndexAttnBlockFunc(torch.autograd.Function):
             ctx, dout, ctx.needs_input_grad[6]
         )
         return _input_grads(IndexAttnBlockFunc, q=dq, k=dk, v=dv, sink=dsink)
+
+
+class IndexAttnKBlockFunc(torch.autograd.Function):
+    """The node of an index call with k_block_size > 1: IndexAttnBlockFunc's
+    inputs and outputs plus k_block_size (q_block_size may be 1 here), which
+    reaches the KBLOCK kernels of the forward and of the backward. The entries
+    of indices_2d are K block ids. fp8 inputs (q_block_size 1) run the fp8
+    KBLOCK forward and, by the upcast policy of IndexAttnFunc, the bf16 KBLOCK
+    backward. The nodes above keep their inputs, so a k_block_size = 1 call
+    builds the graph it always built."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, indices_2d, softmax_scale, softcap,
+                sink, sink_layout, return_max_logits, q_block_size,
+                k_block_size):
+        return _index_attn_forward(
+            ctx, q, k, v, indices_2d, softmax_scale, softcap,
+            sink, sink_layout, return_max_logits, q_block_size, k_block_size,
+        )
+
+    @staticmethod
+    def backward(ctx, dout, *_):
+        dq, dk, dv, dsink = _index_attn_backward(
+            ctx, dout, ctx.needs_input_grad[6]
+        )
+        return _input_grads(IndexAttnKBlockFunc, q=dq, k=dk, v=dv, sink=dsink)
 
 
 def _flex_flash_attn_backward(
@@ -852,7 +911,7 @@ def flex_flash_attn_func(
     meta.max_logits is the per-head f32 [hq] maximum scaled (softcapped)
     logit over valid slots (-inf if there is none), hq <= 128, and the sink
     logits do not enter it.
-    q_block_size = B > 1 (index path, bf16; k_block_size stays 1): the q rows
+    q_block_size = B > 1 (index path, bf16): the q rows
     [b*B, min((b+1)*B, total_q)), with all their hq heads, share the list
     index_attn_indices.reshape(-1, max_topk)[b], so the tensor holds
     ceil(total_q / B) lists, not total_q (asserted; the last block may be
@@ -872,6 +931,31 @@ def flex_flash_attn_func(
     tiles are full already and B = 4 is level (1.03x / 1.00x), no shape
     measured loses. fp8 inputs with q_block_size > 1 are refused. B = 1
     runs the per-token kernels, unchanged.
+    k_block_size = Bk > 1 (index path; a power of two; bf16 with any
+    q_block_size, fp8 with q_block_size 1): the entries of
+    index_attn_indices are K BLOCK ids, id j standing for rows [j*Bk,
+    min((j+1)*Bk, total_k)) of k / v as passed; -1 stays contiguous tail
+    padding and the shape rules are unchanged. When total_k % Bk != 0 the
+    last block is short, may sit anywhere in a list, and its missing rows
+    contribute nothing; an id outside [0, ceil(total_k / Bk)) is masked like
+    an out-of-range row id. The alignment rule becomes (max_topk * Bk) % 64
+    == 0 (Bk = 64 allows any max_topk) and max_topk * Bk must fit int32;
+    Bk = 1 keeps 64 | max_topk and today's kernels. With KV heads folded into
+    the row dimension a block is Bk consecutive rows of the tensor: laying
+    rows out so that a block belongs to one KV head is the caller's
+    business. The kernels walk row positions and form the rows themselves
+    (one wave-uniform id plus lane offsets where a staged group lies in one
+    block); nothing is expanded on the host. softcap, sink, dsink,
+    return_max_logits, padded head dims and q_block_size compose as on the
+    per-token path; deterministic=True with a gradient and fp8 with
+    q_block_size > 1 stay refused. Results agree with the Bk = 1 call over
+    the lists expanded to row ids within rounding, not bit for bit. Measured
+    on an MI355X against that expanded call (d 128, 16k tokens, 2048 rows,
+    hq 8 and 32, (Bk, B) in (16,1), (64,1), (64,16), (128,64);
+    profiles/index_k_block.md): the forward LOSES at every shape, 0.84x to
+    0.92x of the expanded call's speed; the backward is level (0.96x to
+    1.04x). What the block call saves is the index tensor (Bk times smaller),
+    the host expansion and the 64-entry padding, not time.
 
     On the range path q/k/v may also be all float16: out and the gradients
     come back in fp16, lse / max_logits / dsink math stays f32, and every
@@ -1030,10 +1114,6 @@ def flex_flash_attn_func(
             f"index_attn_indices must be 3D (total_q, num_kv_heads, max_topk), "
             f"got shape {tuple(index_attn_indices.shape)}"
         )
-        assert k_block_size == 1, (
-            "only k_block_size=1 (token granularity on the K side) is "
-            "supported for index_attn"
-        )
         assert q_block_size >= 1, (
             f"q_block_size must be >= 1, got {q_block_size}"
         )
@@ -1042,10 +1122,7 @@ def flex_flash_attn_func(
             "not supported with it"
         )
         max_topk = index_attn_indices.shape[2]
-        assert max_topk % 64 == 0, (
-            f"index_attn max_topk={max_topk} must be a multiple of 64 "
-            f"(pad with -1)"
-        )
+        _check_k_block_size(k_block_size, max_topk)
         n_q_blocks = -(-q.shape[0] // q_block_size)
         assert q_block_size == 1 or (
             index_attn_indices.numel() == n_q_blocks * max_topk
@@ -1077,6 +1154,13 @@ def flex_flash_attn_func(
             assert q.shape[1] <= 128, "num_qheads must be <= 128 (reference cap)"
 
         def _index_call(q_, k_, v_):
+            if needs_grad and k_block_size != 1:
+                out_, lse_, ml_ = IndexAttnKBlockFunc.apply(
+                    q_, k_, v_, indices_2d, softmax_scale, softcap,
+                    sink, sink_layout, return_max_logits, q_block_size,
+                    k_block_size,
+                )
+                return out_, AttnForwardMeta(lse=lse_, max_logits=ml_)
             if needs_grad and q_block_size != 1:
                 out_, lse_, ml_ = IndexAttnBlockFunc.apply(
                     q_, k_, v_, indices_2d, softmax_scale, softcap,
@@ -1099,7 +1183,7 @@ def flex_flash_attn_func(
             return _flex_flash_attn_forward_index(
                 q_, k_, v_, indices_2d, softmax_scale, softcap,
                 sink=sink, sink_layout=sink_layout, max_logits=ml_,
-                q_block_size=q_block_size,
+                q_block_size=q_block_size, k_block_size=k_block_size,
             )
 
         d = q.shape[-1]
