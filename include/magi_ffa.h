@@ -200,6 +200,47 @@ typedef struct magi_ffa_fwd_sparse_args {
 int magi_ffa_fwd_sparse(const magi_ffa_fwd_sparse_args* args);
 int magi_ffa_fwd_sparse_args_size(void);
 
+/* swap_ab (reference flex_flash_attn_func swap_ab: fill the matrix units when
+ * q blocks are small, 8 to 64 rows). In magi_ffa_fwd a wave owns 32 q rows and
+ * a workgroup 32 * waves rows of ONE q range, so a range of 32 rows or fewer
+ * has one computing wave per workgroup. pack_gqa fills the rest with the
+ * group's heads; with hq == hk there is no group. This entry fills it with
+ * the k loop. The switch rides behind an embedded copy, as pack_gqa does:
+ *   swap_ab   0: exactly magi_ffa_fwd(&args), bit for bit; reserved is not
+ *             read.
+ *             1: the split-k forward. A 4-wave workgroup owns QT q tiles of 32
+ *             rows of a range (QT = 2; MAGI_FWD_SPLITK_QT = 1 | 2 overrides for
+ *             the A/B, both are correct for any range length; QT = 1 measured
+ *             slower even on 16-row ranges). The KS = 4 / QT waves of a tile split every
+ *             staged K/V image of 32 * KS rows between them, 32 rows each,
+ *             keep a softmax state each and merge the states once per
+ *             (unique) q range, in LDS, in ascending wave order: the result
+ *             repeats run to run. out, lse and max_logits have the usual
+ *             layout and meaning and are within rounding of magi_ffa_fwd's,
+ *             not bit-equal (the summation order over k differs). Every
+ *             member of args keeps its meaning: qk_starts (the states are
+ *             carried across a range's k segments), all four mask types,
+ *             softcap, both element types, GQA (kh = h / (hq / hk), unpacked),
+ *             merge / direct 16-bit / direct f32 out, max_logits, cu_margin.
+ *             Built for d = 64 and 128; d = 192 runs the swap_ab = 0 launch
+ *             and is not an error. MAGI_FWD_WAVES and MAGI_FWD_NBUF are not
+ *             read (4 waves, a 2-slot ring); MAGI_FWD_HEADMAJOR is.
+ *   reserved  must be 0.
+ * Validation with swap_ab = 1, in this order, all before any HIP call: -1
+ * null pointer, -2 head dim, -3 hq % hk != 0, -9 elem_type, -14 reserved != 0;
+ * then n_ranges <= 0 returns 0 without a launch; -4 merge mode without locks,
+ * -5 more than 65535 ranges, -10 merge mode into a 16-bit out. There is no
+ * fp8, pack_gqa or sparse_load combination. magi_ffa_fwd_splitk_args_size is
+ * sizeof of the struct as compiled. */
+typedef struct magi_ffa_fwd_splitk_args {
+  magi_ffa_fwd_args args;
+  int32_t swap_ab;
+  int32_t reserved;         /* must be 0 */
+} magi_ffa_fwd_splitk_args;
+
+int magi_ffa_fwd_splitk(const magi_ffa_fwd_splitk_args* args);
+int magi_ffa_fwd_splitk_args_size(void);
+
 typedef struct magi_ffa_bwd_args {
   const void* dout;         /* elem_type [total_q, hq, d] */
   const void* q;            /* elem_type [total_q, hq, d] */

@@ -85,6 +85,19 @@ class MagiFfaFwdSparseArgs(MagiFfaFwdPackArgs):
     ]
 
 
+class MagiFfaFwdSplitkArgs(MagiFfaFwdArgs):
+    """mirrors magi_ffa_fwd_splitk_args: magi_ffa_fwd_args embedded first, then
+    the swap_ab switch of magi_ffa_fwd_splitk. An instance also passes as the
+    MagiFfaFwdArgs it starts with."""
+
+    _fields_ = [
+        # 1: the waves of a workgroup split the k loop of one or two 32-row q
+        # tiles and merge their softmax states; 0: magi_ffa_fwd's launch
+        ("swap_ab", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),  # must be 0
+    ]
+
+
 class MagiFfaBwdArgs(ctypes.Structure):
     _fields_ = [
         ("dout", ctypes.c_void_p),
@@ -364,6 +377,8 @@ def _try_load() -> ctypes.CDLL | None:
             ("magi_ffa_fwd_pack_args_size", []),
             ("magi_ffa_fwd_sparse", [ctypes.POINTER(MagiFfaFwdSparseArgs)]),
             ("magi_ffa_fwd_sparse_args_size", []),
+            ("magi_ffa_fwd_splitk", [ctypes.POINTER(MagiFfaFwdSplitkArgs)]),
+            ("magi_ffa_fwd_splitk_args_size", []),
             ("magi_ffa_fwd_index", [ctypes.POINTER(MagiFfaIndexArgs)]),
             ("magi_ffa_fwd_index_fp8", [ctypes.POINTER(MagiFfaIndexArgs)]),
             ("magi_ffa_bwd_index", [ctypes.POINTER(MagiFfaIndexBwdArgs)]),
@@ -436,6 +451,7 @@ def _try_load() -> ctypes.CDLL | None:
         for cls, size in [
             (MagiFfaFwdPackArgs, lib.magi_ffa_fwd_pack_args_size()),
             (MagiFfaFwdSparseArgs, lib.magi_ffa_fwd_sparse_args_size()),
+            (MagiFfaFwdSplitkArgs, lib.magi_ffa_fwd_splitk_args_size()),
             (MagiFfaBwdDirectArgs, lib.magi_ffa_bwd_direct_args_size()),
             (MagiFfaBwdCatArgs, lib.magi_ffa_bwd_cat_args_size()),
             (MagiFfaBwdSparseArgs, lib.magi_ffa_bwd_sparse_args_size()),

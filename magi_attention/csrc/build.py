@@ -36,6 +36,7 @@ HEADERS = [
     CSRC / "ffa_device.h",
     CSRC / "ffa_bwd_dq_body.h",
     CSRC / "ffa_bwd_common.h",
+    CSRC / "ffa_fwd_splitk_body.h",
     PKG.parent / "include" / "magi_ffa.h",
 ]
 

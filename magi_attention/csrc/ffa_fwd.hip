@@ -678,6 +678,9 @@ __attribute__((target("no-packed-fp32-ops"))) void ffa_fwd_sparse_kernel(
   ffa_fwd_body<ET, D, HAS_SOFTCAP, ATOMIC, OUT_16, WAVES, NBUF, PACK, true>(p);
 }
 
+// The split-k forward (swap_ab): a body and an entry of its own.
+#include "ffa_fwd_splitk_body.h"
+
 // ------------------------------------------------------------------
 // MFMA layout probe (GPU self-test; see tests/test_ffa_gpu.py)
 // ------------------------------------------------------------------
@@ -729,8 +732,10 @@ extern "C" int magi_probe_mfma(const void* a, const void* b, void* d,
 // ------------------------------------------------------------------
 // launcher
 // ------------------------------------------------------------------
+// SPLITK_QT != 0: the split-k kernel with that many q tiles (W = 4; NB, PACK
+// and SPARSE are not read)
 template <class ET, int D, int W, int NB, bool PACK = false,
-          bool SPARSE = false>
+          bool SPARSE = false, int SPLITK_QT = 0>
 static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams<ET>& p,
                         dim3 grid, dim3 block, hipStream_t stream) {
   const bool sc = a->softcap > 0.f;
@@ -739,7 +744,11 @@ static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams<ET>& p,
   if (atomic && o16) return -10;  // atomic merge requires fp32 out
 #define LAUNCH(SC, AT, OB)                                                 \
   do {                                                                     \
-    if constexpr (SPARSE)                                                  \
+    if constexpr (SPLITK_QT != 0)                                          \
+      hipLaunchKernelGGL(                                                  \
+          (ffa_fwd_splitk_kernel<ET, D, SC, AT, OB, SPLITK_QT>), grid,     \
+          block, 0, stream, p);                                            \
+    else if constexpr (SPARSE)                                             \
       hipLaunchKernelGGL(                                                  \
           (ffa_fwd_sparse_kernel<ET, D, SC, AT, OB, W, NB, PACK>), grid,   \
           block, 0, stream, p);                                            \
@@ -764,9 +773,11 @@ static int launch_fwd_d(const magi_ffa_fwd_args* a, const FwdParams<ET>& p,
 // magi_ffa_fwd past its validation, for one element type. pack: the PACK
 // kernel (magi_ffa_fwd_pack with pack_gqa set and hq != hk). k_cum: non-null
 // picks the SPARSE kernel (magi_ffa_fwd_sparse with sparse_load set, d != 192).
+// splitk: the split-k kernel (magi_ffa_fwd_splitk with swap_ab set, d != 192;
+// neither pack nor k_cum).
 template <class ET>
 static int fwd_entry(const magi_ffa_fwd_args* a, bool pack = false,
-                     const int32_t* k_cum = nullptr) {
+                     const int32_t* k_cum = nullptr, bool splitk = false) {
   const bool sparse = k_cum != nullptr;
   FwdParams<ET> p;
   p.q = (const ET*)a->q;
@@ -806,7 +817,18 @@ static int fwd_entry(const magi_ffa_fwd_args* a, bool pack = false,
   if ((pack || sparse) && max_rows <= 128) fw = 4;
   { const char* e = getenv("MAGI_FWD_WAVES"); if (e && atoi(e)) fw = atoi(e); }
   if (a->d == 192) fw = 4;  // the W8 D=192 build spills (256-reg cap)
-  const int span = 32 * fw;
+  // splitk: 4 waves own QT q tiles of 32 rows and split the k loop KS = 4 / QT
+  // ways. Two tiles whatever the range length: measured, QT = 1 loses even
+  // where the second tile is empty (16- and 32-row ranges), because its
+  // 128-row stages need a 128 KB ring at d = 128, one workgroup per CU where
+  // QT = 2 runs two (profiles/fwd_swap_ab.md). QT = 1 stays built for the A/B.
+  int qt = 2;
+  if (splitk) {
+    const char* e = getenv("MAGI_FWD_SPLITK_QT");  // tests and A/B
+    if (e && (atoi(e) == 1 || atoi(e) == 2)) qt = atoi(e);
+    fw = 4;
+  }
+  const int span = splitk ? 32 * qt : 32 * fw;
   const int mblocks = (int)((max_rows + span - 1) / span);
   const int heads = pack ? a->hk : a->hq;  // head dimension of the work space
   if (a->n_ranges > 65535) return -5;
@@ -828,7 +850,9 @@ static int fwd_entry(const magi_ffa_fwd_args* a, bool pack = false,
   if (margin > 0) {
     // persistent-strided: cap resident WGs to (256 - margin) CUs
     const long long total = (long long)grid.x * grid.y * grid.z;
-    const int per_cu = (fw == 4) ? 2 : 1;
+    // splitk: the 2-slot ring of 32 * KS-row stages, 128 KB at d = 128, QT = 1
+    const int per_cu =
+        splitk ? ((a->d == 128 && qt == 1) ? 1 : 2) : (fw == 4) ? 2 : 1;
     long long cap = (long long)(256 - margin) * per_cu;
     if (cap < 1) cap = 1;
     if (cap > total) cap = total;
@@ -844,6 +868,15 @@ static int fwd_entry(const magi_ffa_fwd_args* a, bool pack = false,
   // pack is built for each (D, WAVES) pair's default ring depth only, to keep
   // the instantiation count in hand: MAGI_FWD_NBUF is not read under pack
   // sparse likewise, for d = 64 and 128, with pack off and on
+  if (splitk) {
+#define SPLITK_LAUNCH(DD)                                                     \
+  (qt == 1 ? launch_fwd_d<ET, DD, 4, 2, false, false, 1>(a, p, grid, block,  \
+                                                         stream)             \
+           : launch_fwd_d<ET, DD, 4, 2, false, false, 2>(a, p, grid, block,  \
+                                                         stream))
+    return a->d == 64 ? SPLITK_LAUNCH(64) : SPLITK_LAUNCH(128);
+#undef SPLITK_LAUNCH
+  }
   if (sparse) {
 #define SPARSE_LAUNCH(DD, PK)                                                \
   (fw == 8 ? launch_fwd_d<ET, DD, 8, 3, PK, true>(a, p, grid, block, stream) \
@@ -933,6 +966,28 @@ extern "C" int magi_ffa_fwd_sparse(const magi_ffa_fwd_sparse_args* sa) {
 
 extern "C" int magi_ffa_fwd_sparse_args_size(void) {
   return (int)sizeof(magi_ffa_fwd_sparse_args);
+}
+
+extern "C" int magi_ffa_fwd_splitk(const magi_ffa_fwd_splitk_args* sa) {
+  if (!sa) return -1;
+  const magi_ffa_fwd_args* a = &sa->args;
+  if (!sa->swap_ab) return magi_ffa_fwd(a);
+  if (!a->q || !a->k || !a->v || !a->out || !a->lse) return -1;
+  if (a->d != 64 && a->d != 128 && a->d != 192) return -2;
+  if (a->hq % a->hk != 0) return -3;
+  if (!elem_type_known(a->elem_type)) return -9;
+  if (sa->reserved != 0) return -14;
+  if (a->n_ranges <= 0) return 0;
+  if (!a->disable_atomic_reduction && !a->locks) return -4;
+  // no split-k build at d = 192: the default launch
+  const bool splitk = a->d != 192;
+  return a->elem_type == MAGI_FFA_ELEM_FP16
+             ? fwd_entry<f16_t>(a, false, nullptr, splitk)
+             : fwd_entry<bf16_t>(a, false, nullptr, splitk);
+}
+
+extern "C" int magi_ffa_fwd_splitk_args_size(void) {
+  return (int)sizeof(magi_ffa_fwd_splitk_args);
 }
 
 extern "C" int magi_ffa_args_size(int which) {

@@ -155,6 +155,17 @@ def sparse_load_active(sparse_load, dtype: torch.dtype, d: int,
             and d in (64, 128))
 
 
+def swap_ab_active(swap_ab, dtype: torch.dtype, d: int, pack: bool,
+                   sparse: bool) -> bool:
+    """Whether a forward with this flag runs the split-k kernel: there is one
+    built for it (16-bit, d = 64 or 128) and neither pack_gqa nor sparse_load
+    is active (pack, sparse: their *_active results). Where one of them is,
+    its kernel runs; otherwise the flag is accepted and the default launch
+    runs."""
+    return (bool(swap_ab) and dtype in (torch.bfloat16, torch.float16)
+            and d in (64, 128) and not pack and not sparse)
+
+
 def fp8_flex_active(dtype: torch.dtype, softcap, qk_starts,
                     disable_fwd_atomic_reduction) -> bool:
     """Whether an fp8 forward goes to magi_ffa_fwd_fp8_flex: it asks for
@@ -168,20 +179,25 @@ def fp8_flex_active(dtype: torch.dtype, softcap, qk_starts,
 def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
         max_logits, qk_starts, max_seqlen_q, softmax_scale, softcap,
         disable_fwd_atomic_reduction, sm_margin, deterministic,
-        pack_gqa=False, sparse_load=False) -> None:
+        pack_gqa=False, sparse_load=False, swap_ab=False) -> None:
     """Dense forward into (out, lse): an fp8 entry (the flex one where
     fp8_flex_active) or the 16-bit one (bf16 or fp16 by elem_type) by q.dtype;
     deterministic = fixed merge order, one launch per q-disjoint range group;
     pack_gqa = a workgroup owns a KV head and packs the (token, q head) pairs
     of its group into its q tiles (where pack_gqa_active);
     sparse_load = the k segments of a unique q range are packed into full K/V
-    tiles (where sparse_load_active; every segment must be a full block)."""
+    tiles (where sparse_load_active; every segment must be a full block);
+    swap_ab = the four waves of a workgroup split the k loop of one or two
+    32-row q tiles and merge their softmax states (where swap_ab_active)."""
     tq, hq, d = q.shape
     tk, hk, _ = k.shape
     pack = pack_gqa_active(pack_gqa, q.dtype, hq, hk)
     sparse = sparse_load_active(sparse_load, q.dtype, d, qk_starts)
+    splitk = swap_ab_active(swap_ab, q.dtype, d, pack, sparse)
     args = (_ffa_lib.MagiFfaFwdSparseArgs if sparse else
-            _ffa_lib.MagiFfaFwdPackArgs if pack else _ffa_lib.MagiFfaFwdArgs)(
+            _ffa_lib.MagiFfaFwdPackArgs if pack else
+            _ffa_lib.MagiFfaFwdSplitkArgs if splitk else
+            _ffa_lib.MagiFfaFwdArgs)(
         q=ptr(q), k=ptr(k), v=ptr(v), out=ptr(out), lse=ptr(lse),
         q_ranges=ptr(q_ranges), k_ranges=ptr(k_ranges),
         attn_type_map=ptr(attn_type_map), locks=ptr(locks),
@@ -216,6 +232,9 @@ def fwd(q, k, v, out, lse, q_ranges, k_ranges, attn_type_map, *, locks,
         args.k_cum = ptr(k_cum)
         args.sparse_load = 1
         fn = lib.magi_ffa_fwd_sparse
+    if splitk:  # looked up only here: a library without the entry still serves
+        args.swap_ab = 1
+        fn = lib.magi_ffa_fwd_splitk
     if deterministic and q_ranges.shape[0] > 1:
         groups = _color_ranges(q_ranges.cpu().tolist())
         launch_per_group(args, q_ranges, k_ranges, attn_type_map,

@@ -121,6 +121,7 @@ def _flex_flash_attn_forward(
     qk_starts: Optional[torch.Tensor] = None,
     pack_gqa: bool = False,
     sparse_load: bool = False,
+    swap_ab: bool = False,
     **_unused,
 ) -> tuple[torch.Tensor, AttnForwardMeta]:
     """Dense (range-table) forward into (out, lse). q/k/v are all bf16, all
@@ -137,6 +138,9 @@ def _flex_flash_attn_forward(
     launch otherwise - for fp8 that is the fp8 kernel's own segment loop;
     with the sparse kernel every k segment must be a full block (type 0),
     which is not checked.
+    swap_ab runs the split-k kernel where _ffa_launch.swap_ab_active says so
+    (bf16 / fp16, d 64 or 128, neither of the two kernels above) and the
+    launch the other flags pick otherwise.
 
     fp16 direct store with a sink: the sink postprocess kernel reads a 16-bit
     out as bf16, so it must never see fp16. That combination therefore runs
@@ -202,7 +206,7 @@ def _flex_flash_attn_forward(
         softcap=softcap,
         disable_fwd_atomic_reduction=disable_fwd_atomic_reduction,
         sm_margin=sm_margin, deterministic=deterministic, pack_gqa=pack_gqa,
-        sparse_load=sparse_load,
+        sparse_load=sparse_load, swap_ab=swap_ab,
     )
     if sink is not None:
         assert out.dtype != torch.float16  # the postprocess reads 16 bits as bf16
@@ -798,7 +802,7 @@ class FlexFlashAttnFunc(torch.autograd.Function):
             deterministic=deterministic, sm_margin=sm_margin,
             max_seqlen_q=max_seqlen_q, max_logits=max_logits,
             qk_starts=fwd_qk_starts, pack_gqa=pack_gqa,
-            sparse_load=sparse_load,
+            sparse_load=sparse_load, swap_ab=swap_ab,
         )
         lse = meta.lse
         # fp8 extension returns bf16 out
@@ -1017,6 +1021,30 @@ def flex_flash_attn_func(
     below 64 rows, the crossover lying between 64 and 128; in merge mode only
     at 16 rows.
 
+    swap_ab=True (range path, bf16 / fp16, head dims up to 128; reference:
+    fill the matrix units when q blocks are small): the default forward gives
+    a wave 32 q rows of ONE q range, so a range of 32 rows or fewer has one
+    computing wave in a 512-thread workgroup, and with hq == hk pack_gqa has
+    no group to fill it with. With the flag a 4-wave workgroup owns two 32-row
+    q tiles of a (unique) q range; the two waves of a tile take alternate
+    32-row halves of every 64-row K/V stage, keep a softmax state each -
+    across the k ranges of a q range under auto_range_merge - and merge the
+    states once, in LDS, in a fixed order. out, lse and max_logits agree with
+    the default launch within rounding (not bit for bit) and repeat run to
+    run; all four mask types, softcap, sink, GQA (unpacked), direct store,
+    sm_margin, deterministic, return_max_logits and padded head dims compose
+    with it, and the backward is the usual one. Where pack_gqa or sparse_load
+    is active, that kernel runs and the flag has no effect; fp8 inputs, head
+    dims above 128 and index_attn_indices accept it and run what they run
+    without it; the context-parallel runtime does not pass it. Measured
+    (profiles/fwd_swap_ab.md; block-sparse MHA, 16k tokens, 8 heads, d 128,
+    a quarter of the 128-row k blocks per q block, auto_range_merge; 32 heads
+    within 0.12 of these): the forward takes 0.34x / 0.40x / 0.41x / 0.80x the
+    default's time at q blocks of 16 / 32 / 64 / 128 rows with the direct
+    store and 0.53x / 0.64x / 0.51x / 1.16x in merge mode; at 256 rows 1.38x /
+    2.0x, on a dense causal 16k mask 1.24x / 1.61x. It pays up to 64-row q
+    ranges, up to 128 with the direct store, and costs beyond: off by default.
+
     sparse_load_bwd=True (a switch of its own: sparse_load alone leaves the
     backward as it is; it requires sparse_load=True, RuntimeError otherwise)
     does the same to the dQ pass of the backward: the dQ kernel lays the k
@@ -1231,7 +1259,7 @@ def flex_flash_attn_func(
             return_max_logits=return_max_logits,
             pack_gqa=pack_gqa, cat_gqa=cat_gqa, sparse_load=sparse_load,
             sparse_load_bwd=sparse_load_bwd,
-            swap_bwd_qk_loop=swap_bwd_qk_loop,
+            swap_bwd_qk_loop=swap_bwd_qk_loop, swap_ab=swap_ab,
         )
         return out[..., :d], meta
     out, lse, max_logits = FlexFlashAttnFunc.apply(
